@@ -10,7 +10,13 @@ environment; the reference's recipe, bash_scripts/tulip_upsampling_kitti.sh:35 +
 launcher set WORLD_SIZE, bench.py starts the N ranks itself through the same module (spawn_ranks).  Rank 0 prints ONE
 JSON line.
 
-Extra objects:  "roofline" -- the dominant kernel (the bf16 MFMA GEMM family): algorithmic FLOPs of
+A plain run only sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` also writes what the last
+timed step handed its caller (step_outputs) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+
+`--full` adds the measurements beside the headline (N=1, rank 0; each can be dropped with its --no-* option):  "secondary" /
+"secondary_fp8_attention" -- the step at batch 64, bf16 and fp8 attention scores;  "secondary_reference_loop" -- the
+reference's own loop body on the drop-in module;  "secondary_eval_forward" -- the graphed eval forward at batch 8 and 64;
+"roofline" -- the dominant kernel (the bf16 MFMA GEMM family): algorithmic FLOPs of
 its launches in one step / their summed duration, each launch bracketed by HIP events on the launch
 stream in a separate eager pass (graphs cannot be instrumented per node);  "cpu_baseline" -- the
 oracle (plain PyTorch fp32 restatement of the reference, oracle/tulip_oracle.py) running the same
@@ -600,6 +606,26 @@ def reference_loop(args, device, steps=40, warmup=5):
             "steps": steps, "warmup": warmup, "final_loss": round(v, 6), "grad_scale": scaler.get_scale()}
 
 
+DUMP_SAMPLE = 1 << 22      # values per dumped array at most (16 MB of float32): larger outputs are sampled
+
+
+def step_outputs(trainer, losses):
+    """What the last timed step handed its caller, on the host as float32: `loss` ([loss, pixel_loss], what Trainer.step
+    returns), `pred` (the prediction of that step) and `params` (the parameters after its optimizer step, every tensor in name
+    order, padding left out).  An array longer than DUMP_SAMPLE is replaced by the same seeded sample of its values in every run.
+    A collective for exchange="sharded" (gather_state): every rank calls it."""
+    trainer.gather_state()
+    W = trainer.eng.params
+    out = {"loss": losses, "pred": trainer.P.pred,
+           "params": torch.cat([W.flat[W.offset[n]:W.offset[n] + W.numel[n]] for n in sorted(W.names)])}
+    for k, t in out.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[k] = t.float().cpu().numpy()
+    return out
+
+
 def secondary_eval_forward(args, device, iters=50, warmup=5):
     """SURVEY 8(d) "Secondary: eval-forward images/s" -- the reference's call site is engine_upsampling.py:168-171
     (`model(images_low_res, images_high_res, eval=True)` under no_grad) and the MC-dropout tile of 8 (:417-419).  The eval
@@ -687,6 +713,11 @@ def main():
                          "never the default: reduce-scatter -> AdamW on the owned shard -> all-gather of the bf16 shadow, "
                          "tulip_amd.ddp.ShardedExchange)")
     ap.add_argument("--bucket-mb", type=float, default=16.0)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also the batch-64, reference-loop, eval-forward, roofline and CPU-baseline measurements (off: the "
+                         "headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (loss, prediction, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
@@ -797,7 +828,9 @@ def main():
             tmax = torch.tensor([dt_], device=device, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt_ = tmax.item()
-        return tr, dt_, ps, ls
+        # (taken here: the N > 1 comm report steps on, and a plan measured later may lose to this one)
+        outs = step_outputs(tr, ls) if args.dump_outputs else None
+        return tr, dt_, ps, ls, outs
 
     def drop(tr):
         trainer_ref[0] = None
@@ -806,7 +839,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    trainer, dt, per_step, losses = run_plan(grad_dtype, bucket_adamw)
+    trainer, dt, per_step, losses, outputs = run_plan(grad_dtype, bucket_adamw)
     comm = None
     if world > 1:
         phase("replica_check")
@@ -820,7 +853,7 @@ def main():
             os.environ["TULIP_DETACH_BUCKETS"] = "0"
             grad_dtype, bucket_adamw = "fp32", False
             args.exchange = "allreduce"
-            trainer, dt, per_step, losses = run_plan(grad_dtype, bucket_adamw)
+            trainer, dt, per_step, losses, outputs = run_plan(grad_dtype, bucket_adamw)
             same = replicas_identical(trainer, device)
         phase("comm_report")
         comm = comm_report(trainer, args, world, device)
@@ -832,18 +865,18 @@ def main():
                  and grad_dtype == "fp32" and comm["exposed_exchange_ms"] > max(0.15, 0.07 * step_ms))
         if adapt:
             # the prediction said fp32 hides; the measurement says it does not: measure the bf16 exchange as well
-            keep = (trainer.bucket_adamw, dt, per_step, losses, comm)
+            keep = (trainer.bucket_adamw, dt, per_step, losses, comm, outputs)
             drop(trainer)
-            trainer, dt2, per2, losses2 = run_plan("bf16", bucket_adamw)
+            trainer, dt2, per2, losses2, outputs2 = run_plan("bf16", bucket_adamw)
             same2 = replicas_identical(trainer, device)
             comm2 = comm_report(trainer, args, world, device)
             comm2["replicas_identical"] = same2
             plans_tried.append({"grad_dtype": "bf16", "bucket_adamw": bool(trainer.bucket_adamw),
                                 "ms_per_step": round(dt2 / args.steps * 1e3, 4), "exposed_exchange_ms": comm2["exposed_exchange_ms"]})
             if same2 and dt2 < 0.97 * dt:
-                grad_dtype, dt, per_step, losses, comm = "bf16", dt2, per2, losses2, comm2
+                grad_dtype, dt, per_step, losses, comm, outputs = "bf16", dt2, per2, losses2, comm2, outputs2
             else:       # fp32 stays the line; the trainer left alive is the bf16 one, which only matters to the roofline (N = 1)
-                _, dt, per_step, losses, comm = keep
+                _, dt, per_step, losses, comm, outputs = keep
     loss_val = losses[0].item()
     if not (loss_val == loss_val and abs(loss_val) < 1e9):
         raise SystemExit(f"non-finite loss {loss_val}")
@@ -917,16 +950,22 @@ def main():
     if attempts or fallback:
         out["graph_path_failed"] = True
         out["attempts"] = attempts
-    if rank == 0 and world == 1 and not args.no_secondary and args.batch == 8 and args.model == "tulip_base":
+    if rank == 0 and outputs is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
+    extra = rank == 0 and world == 1 and args.full
+    if extra and not args.no_secondary and args.batch == 8 and args.model == "tulip_base":
         out["secondary"] = secondary_batch64(args, device)
         out["secondary_fp8_attention"] = secondary_batch64(args, device, attn_fp8=True)
-    if rank == 0 and world == 1 and not args.no_reference_loop and headline:
+    if extra and not args.no_reference_loop and headline:
         out["secondary_reference_loop"] = reference_loop(args, device)
-    if rank == 0 and world == 1 and not args.no_secondary and headline:
+    if extra and not args.no_secondary and headline:
         out["secondary_eval_forward"] = secondary_eval_forward(args, device)
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if extra and not args.no_roofline:
         out["roofline"] = kernel_rooflines(trainer)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if extra and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

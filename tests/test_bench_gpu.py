@@ -1,5 +1,5 @@
-"""GPU: the bench.py contract the driver depends on -- `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with
-the metric of BASELINE.json, the whole-job value, and the `roofline` / `cpu_baseline` objects."""
+"""GPU: the bench.py contract the driver depends on -- `python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line
+with the metric of BASELINE.json, the whole-job value, and the `roofline` / `cpu_baseline` objects."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3", "--full",
                         "--no-secondary", "--cpu-steps", "1", "--cpu-warmup", "0", "--cpu-batch", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -44,3 +44,24 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1
+
+
+def test_plain_run_times_the_headline_step_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline step alone; --dump-outputs writes what the last timed step returned: the loss the
+    line reports, the prediction and the updated parameters (a fixed sample of them), float32, 64 MB at most."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "range-images/s"
+    for k in ("secondary", "secondary_fp8_attention", "secondary_reference_loop", "secondary_eval_forward", "roofline", "cpu_baseline"):
+        assert k not in d, k
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss", "pred", "params")}
+    assert sorted(os.listdir(tmp_path)) == ["loss.npy", "params.npy", "pred.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["loss"].shape == (2,) and abs(float(got["loss"][0]) - d["final_loss"]) <= 1e-6
+    assert got["pred"].shape == (8, 1, 64, 1024) and got["params"].shape == (1 << 22,)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

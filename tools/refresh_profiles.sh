@@ -24,7 +24,7 @@ python tools/instep_summary.py $(find $O/kt -name "*.db" | head -1) $O/instep_du
 cp $O/instep_durations.json profiles/instep_durations.json
 python tools/step_stamps.py 8 $O/step_stamps.json 2>/dev/null | grep -v amdgpu.ids > $O/step_stamps.txt
 cp $O/step_stamps.json profiles/step_stamps.json
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 rocprofv3 --kernel-trace --stats -d $O/kt64 -- python bench.py --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-secondary --no-reference-loop > $O/kt64.log 2>&1
 python tools/kstats.py $(find $O/kt64 -name "*.db" | head -1) 20 > $O/kernel_stats_b64.txt
 python tools/bench_eval.py > $O/eval_bench.json 2>/dev/null

@@ -369,6 +369,50 @@ int tulip_adamw_blocks(float* p, float* g, float* m, float* v, uint16_t* p_bf16,
 int tulip_drop_path_scales(const float* keep, float* scale, float* u_out, int nslots, int B, uint64_t seed,
                            uint64_t* counter, hipStream_t stream);
 
+/* Element dropout (nn.Dropout, tulip.py:190-192, 315, 319, 705): y = x * m / (1-p), m a Bernoulli(1-p) keep mask that is
+ * counter-based -- nothing is stored, the backward regenerates it.  The mask function, bit for bit (host code reproduces it):
+ *   mix64(z)        = splitmix64 finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *                     z ^= z >> 31  (uint64 arithmetic)
+ *   key             = mix64(seed ^ mix64(counter * 2^20 + site))
+ *   u(index)        = mix64(key + index) >> 40                  (top 24 bits)
+ *   kept(index)     = u(index) >= rint(p * 2^24)                (p as fp32, rint = round half to even)
+ *   scale           = 1.0f / (1.0f - p)                          (fp32, correctly rounded)
+ * seed: the engine's DropPath seed; counter: *key_ptr, a device word the forward records once per step (tulip_dropout_begin),
+ * read through the pointer by every dropout launch of that forward and of its backward, so graph replays draw fresh masks;
+ * site: 0 = pos_drop, block i (engine order) 1 + 4 i + {0 attn_drop, 1 proj_drop, 2 mlp.drop1, 3 mlp.drop2};
+ * index: row * cols + c over natural token rows (pos_drop, proj_drop, drop2: cols = C; drop1: cols = hidden), and for
+ * attn_drop ((((b * nWy + wy) * nWx + wx) * nh + head) * 16 + q) * 16 + k, (wy, wx) the window of the rolled image, q / k the
+ * in-window slots i * ww + j -- the flattening of the reference's [B * nW, nh, N, N] probability tensor.  p in [0, 1). */
+/* *key_out = *counter; advance != 0: *counter += 1 (a forward whose DropPath draw does not advance it already) */
+int tulip_dropout_begin(uint64_t* counter, uint64_t* key_out, int advance, hipStream_t stream);
+/* mask read-out: out[i] = kept(i) ? scale : 0, i < n (fp32) */
+int tulip_dropout_mask(const uint64_t* key_ptr, uint64_t seed, int site, float p, int64_t n, float* out, hipStream_t stream);
+/* in place: x[r * ld + c] *= kept(r * cols + c) ? scale : 0, x fp32 (is_bf16 = 0) or bf16 (is_bf16 = 1, rounded to nearest
+ * even); cols % 4 == 0, ld % 4 == 0 */
+int tulip_dropout_scale(void* x, int is_bf16, int rows, int cols, int ld, const uint64_t* key_ptr, uint64_t seed, int site,
+                        float p, hipStream_t stream);
+/* residual with dropout (proj_drop / drop2 of a block; y = the fp32 Linear output incl. bias, TULIP_EPI_F32):
+ * out = aux + rowscale[r / rows_per_sample] * (y * (kept ? scale : 0)) ([rows][C], y may alias out), out_bf16 (optional)
+ * = bf16(out), and, gamma != NULL, the LayerNorm behind it exactly as tulip_layernorm_fwd computes it (xn, mean, rstd).
+ * rowscale may be NULL.  C % 4 == 0. */
+int tulip_dropout_resid_ln(const float* y, const float* aux, const float* rowscale, int rows_per_sample, float* out,
+                           uint16_t* out_bf16, const float* gamma, const float* beta, uint16_t* xn, float* mean, float* rstd,
+                           float eps, int rows, int C, const uint64_t* key_ptr, uint64_t seed, int site, float p,
+                           hipStream_t stream);
+/* backward of the above: y = bf16(dx * rowscale[r / rows_per_sample] * (kept ? scale : 0)), [rows][cols]; rowscale may be NULL */
+int tulip_dropout_cast(const float* dx, uint16_t* y, int rows, int cols, const float* rowscale, int rows_per_sample,
+                       const uint64_t* key_ptr, uint64_t seed, int site, float p, hipStream_t stream);
+/* tulip_window_attn_fwd / _bwd with attn_drop on the softmax probabilities (P.V from the dropped probabilities; backward:
+ * dV from the dropped probabilities, dP = (dO.V^T) * mask * scale, dS = P * (dP - rowsum(dP * P))).  `masked` bit 1 (fp8
+ * scores) is refused with TULIP_ERR_ARG before anything is launched. */
+int tulip_window_attn_fwd_drop(const uint16_t* qkv, const float* bias_table, const int32_t* rel_index, uint16_t* out, int B,
+                               int H, int W, int C, int nh, int wh, int ww, int sh, int sw, int masked,
+                               const uint64_t* key_ptr, uint64_t seed, int site, float p, hipStream_t stream);
+int tulip_window_attn_bwd_drop(const uint16_t* qkv, const uint16_t* dout, const float* bias_table, const int32_t* rel_index,
+                               uint16_t* dqkv, float* dbias_partials, int B, int H, int W, int C, int nh, int wh, int ww,
+                               int sh, int sw, int masked, const uint64_t* key_ptr, uint64_t seed, int site, float p,
+                               hipStream_t stream);
+
 /* Gradient L2 norm read-out (misc.py:317-329 get_grad_norm_, taken before the optimizer step, misc.py:303):
  * out[0] = sqrt(sum g[i]^2) * scale * (scale_dev ? scale_dev[0] : 1).  partials: scratch of 1024 doubles.
  * Fixed partition and fold order: deterministic. */

@@ -154,6 +154,13 @@ SIGNATURES = {
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
     "tulip_drop_path_scales": [P, P, P, I, I, ctypes.c_uint64, P, P],
+    "tulip_dropout_begin": [P, P, I, P],
+    "tulip_dropout_mask": [P, ctypes.c_uint64, I, F, L, P, P],
+    "tulip_dropout_scale": [P, I, I, I, I, P, ctypes.c_uint64, I, F, P],
+    "tulip_dropout_resid_ln": [P, P, P, I, P, P, P, P, P, P, P, F, I, I, P, ctypes.c_uint64, I, F, P],
+    "tulip_dropout_cast": [P, P, I, I, P, I, P, ctypes.c_uint64, I, F, P],
+    "tulip_window_attn_fwd_drop": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, ctypes.c_uint64, I, F, P],
+    "tulip_window_attn_bwd_drop": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, ctypes.c_uint64, I, F, P],
     "tulip_grad_norm": [P, L, P, P, F, P, P],
     "tulip_kitti_range_map": [P, L, I, I, F, F, F, F, F, P, P, P],
     "tulip_range_prep": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, I, P],

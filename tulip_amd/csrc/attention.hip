@@ -64,11 +64,13 @@ __device__ __forceinline__ WaveMap wave_map(int nh, int ngrp) {
     return m;
 }
 
-template <int P>
+// DROP: attn_drop on the probabilities (tulip.py:315), mask element ((window * nh + head) * 16 + query) * 16 + key of the
+// counter-based mask (include/tulip_hip.h, "Element dropout"); DROP = false is the kernel the step runs without it.
+template <int P, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv,
                                                        const float* __restrict__ bias_table,
                                                        const int* __restrict__ rel_index, bf16_t* __restrict__ out,
-                                                       AttnGeom g, int ngrp) {
+                                                       AttnGeom g, int ngrp, DropoutArg da = DropoutArg{}) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 16 * P * 2];
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4;
     unsigned char* ldsV = smem + (threadIdx.x >> 6) * (16 * P * 2);
@@ -82,6 +84,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     float bias[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) bias[r] = bias_table[rel_index[li * 16 + gq * 4 + r] * g.nh + h];
+
+    uint64_t dkey = 0;
+    uint32_t dthr = 0;
+    float dscale = 0.f;
+    if constexpr (DROP) { dkey = dropout_key(da); dthr = dropout_thr(da.p); dscale = dropout_inv_keep(da.p); }
 
     for (int win = wm.grp; win < total; win += ngrp) {
         const int b = fast_div(win, nW), wloc = win - b * nW;
@@ -116,6 +123,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
         for (int r = 0; r < 4; ++r) { s[r] = __expf(s[r] - mx); sum += s[r]; }
         sum = rows_sum(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
+        if constexpr (DROP) {           // lane (query li, key 4gq+r)
+            const uint64_t base = ((uint64_t)win * g.nh + h) * 256 + li * 16 + gq * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[r] *= dropout_mul(dkey, base + r, dthr, dscale);
+        }
         const bf16x4 pb = pack4(s[0] * inv, s[1] * inv, s[2] * inv, s[3] * inv);
         bf16_t* dst = out + (size_t)row * g.C + h * P + gq * 4;
 #pragma unroll
@@ -128,11 +140,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     }
 }
 
-template <int P>
+// DROP: the backward of attn_drop -- dV from the dropped probabilities, dP = (dO.V^T) * mask * scale ahead of the softmax
+// backward, whose row term sum_key P * dP then equals rowsum(dO * O) of the dropped forward.
+template <int P, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                        const float* __restrict__ bias_table,
                                                        const int* __restrict__ rel_index, bf16_t* __restrict__ dqkv,
-                                                       float* dbias_part, AttnGeom g, int ngrp) {
+                                                       float* dbias_part, AttnGeom g, int ngrp, DropoutArg da = DropoutArg{}) {
     // All 4 waves of a workgroup serve the SAME head (blockIdx.x % nh), so d(bias) is summed over the
     // workgroup in LDS and leaves as one plain 256-float partial row per workgroup:
     // dbias_part[blockIdx.x][i*16+j].  Rows of one head are nh apart -> viewed as [gridDim.x/nh][nh*256]
@@ -158,6 +172,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
         bias_k[r] = bias_table[rel_index[(gq * 4 + r) * 16 + li] * g.nh + h];
     }
     float dbacc[4] = {0.f, 0.f, 0.f, 0.f};
+    uint64_t dkey = 0;
+    uint32_t dthr = 0;
+    float dscale = 0.f;
+    if constexpr (DROP) { dkey = dropout_key(da); dthr = dropout_thr(da.p); dscale = dropout_inv_keep(da.p); }
 
     for (int win = wm.grp; win < total; win += ngrp) {
         const int b = fast_div(win, nW), wloc = win - b * nW;
@@ -182,6 +200,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
         f32x4 sk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q, k, z, 0, 0, 0);   // Lk: S[4gq+r][li]
         f32x4 dpq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v, d, z, 0, 0, 0);  // Lq: dP[li][4gq+r] = dO_li . V_key
         f32x4 dpk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d, v, z, 0, 0, 0);  // Lk: dP[4gq+r][li]
+        float mk[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (DROP) {
+            const uint64_t base = ((uint64_t)win * g.nh + h) * 256;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                dpq[r] *= dropout_mul(dkey, base + li * 16 + gq * 4 + r, dthr, dscale);     // Lq: (query li, key 4gq+r)
+                mk[r] = dropout_mul(dkey, base + (gq * 4 + r) * 16 + li, dthr, dscale);    // Lk: (query 4gq+r, key li)
+                dpk[r] *= mk[r];
+            }
+        }
 
         float mx = -3.0e38f;
 #pragma unroll
@@ -216,7 +244,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
         }
         const bf16x4 dsq_b = pack4(dsq[0], dsq[1], dsq[2], dsq[3]);
         const bf16x4 dsk_b = pack4(dsk[0], dsk[1], dsk[2], dsk[3]);
-        const bf16x4 pk_b = pack4(pk[0], pk[1], pk[2], pk[3]);
+        const bf16x4 pk_b = DROP ? pack4(pk[0] * mk[0], pk[1] * mk[1], pk[2] * mk[2], pk[3] * mk[3])
+                                 : pack4(pk[0], pk[1], pk[2], pk[3]);
         bf16_t* dst = dqkv + (size_t)row * C3 + h * P + gq * 4;
         const int troff = (gq * 4 + (li >> 2)) * (P * 2) + (li & 3) * 8;
 #pragma unroll
@@ -310,6 +339,48 @@ extern "C" int tulip_window_attn_bwd(const uint16_t* qkv, const uint16_t* dout, 
     else
         hipLaunchKernelGGL(attn_bwd_kernel<16>, dim3(blocks), dim3(256), 0, stream, qkv, dout, bias_table, rel_index,
                            dqkv, dbias_partials, g, ngrp);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_window_attn_fwd_drop(const uint16_t* qkv, const float* bias_table, const int32_t* rel_index,
+                                          uint16_t* out, int B, int H, int W, int C, int nh, int wh, int ww, int sh, int sw,
+                                          int masked, const uint64_t* key_ptr, uint64_t seed, int site, float p,
+                                          hipStream_t stream) {
+    AttnGeom g;
+    if (!make_geom(g, B, H, W, C, nh, wh, ww, sh, sw, masked)) return TULIP_ERR_ARG;
+    if (g.fp8 || !key_ptr || !(p >= 0.0f && p < 1.0f)) return TULIP_ERR_ARG;      // attn_drop with fp8 scores: not built
+    if (B <= 0) return TULIP_OK;
+    const int ngrp = pick_groups(g);
+    const int blocks = (ngrp * nh + 3) / 4;
+    const DropoutArg da{(const unsigned long long*)key_ptr, (unsigned long long)seed, site, p};
+    if (C / nh == 32)
+        hipLaunchKernelGGL((attn_fwd_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, qkv, bias_table, rel_index, out, g,
+                           ngrp, da);
+    else
+        hipLaunchKernelGGL((attn_fwd_kernel<16, true>), dim3(blocks), dim3(256), 0, stream, qkv, bias_table, rel_index, out, g,
+                           ngrp, da);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_window_attn_bwd_drop(const uint16_t* qkv, const uint16_t* dout, const float* bias_table,
+                                          const int32_t* rel_index, uint16_t* dqkv, float* dbias_partials, int B, int H,
+                                          int W, int C, int nh, int wh, int ww, int sh, int sw, int masked,
+                                          const uint64_t* key_ptr, uint64_t seed, int site, float p, hipStream_t stream) {
+    AttnGeom g;
+    if (!make_geom(g, B, H, W, C, nh, wh, ww, sh, sw, masked)) return TULIP_ERR_ARG;
+    if (g.fp8 || !key_ptr || !(p >= 0.0f && p < 1.0f)) return TULIP_ERR_ARG;
+    if (B <= 0) return TULIP_OK;
+    const int bph = bwd_blocks_per_head(g.B * g.nWy * g.nWx, nh);
+    const int blocks = bph * nh, ngrp = bph * 4;
+    const DropoutArg da{(const unsigned long long*)key_ptr, (unsigned long long)seed, site, p};
+    if (C / nh == 32)
+        hipLaunchKernelGGL((attn_bwd_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, qkv, dout, bias_table, rel_index,
+                           dqkv, dbias_partials, g, ngrp, da);
+    else
+        hipLaunchKernelGGL((attn_bwd_kernel<16, true>), dim3(blocks), dim3(256), 0, stream, qkv, dout, bias_table, rel_index,
+                           dqkv, dbias_partials, g, ngrp, da);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

@@ -97,6 +97,20 @@ __device__ __forceinline__ void drop_draw_block(const DropDraw& d) {
     if (threadIdx.x == 0) *d.counter = c + 1;
 }
 
+// Element dropout mask (include/tulip_hip.h, "Element dropout"): kept(index) = top 24 bits of mix64(key + index) >= rint(p 2^24),
+// key = mix64(seed ^ mix64(counter 2^20 + site)) with the counter read from the step's device word.  Shared by csrc/dropout.hip and
+// the dropout forms of the attention kernels (csrc/attention.hip).
+struct DropoutArg { const unsigned long long* key_ptr; unsigned long long seed; int site; float p; };
+__device__ __forceinline__ uint64_t dropout_key(const DropoutArg& d) {
+    return drop_mix64(d.seed ^ drop_mix64((*d.key_ptr << 20) + (uint64_t)d.site));
+}
+__device__ __forceinline__ uint32_t dropout_thr(float p) { return (uint32_t)__builtin_rintf(p * 16777216.0f); }
+__device__ __forceinline__ float dropout_inv_keep(float p) { return 1.0f / (1.0f - p); }
+// the multiplier of one element: scale if kept, else 0
+__device__ __forceinline__ float dropout_mul(uint64_t key, uint64_t index, uint32_t thr, float scale) {
+    return (uint32_t)(drop_mix64(key + index) >> 40) >= thr ? scale : 0.0f;
+}
+
 // Sum of the `nslab` split-K partial slabs of one float4, in slab order (the order every fold of these slabs uses: same bits).
 // Four loads are issued before the first add -- a loop of load / add pairs with a run-time trip count is a chain of nslab
 // memory latencies, and the kernels that fold (3-4 slabs, a few rows per workgroup) are nothing but that chain.

@@ -57,6 +57,7 @@ class BlockSpec:
     win: Tuple[int, int] = (2, 8)
     sft: Tuple[int, int] = (0, 0)
     slot: int = -1  # row in the DropPath scale table (-1: rate 0)
+    idx: int = -1   # position in TulipEngine.blocks (element-dropout site numbers 1 + 4 idx + kind)
 
 
 class FlatParams:
@@ -291,6 +292,11 @@ class Plan:
         self.drop_scale = self.f32("drop_scale", nslots, B)
         self.drop_scale.fill_(1.0)
         self.drop_u = self.f32("drop_u", nslots, B)
+        # element dropout: the counter value this plan's forward drew its masks with (tulip_dropout_begin), read through its address by
+        # every dropout launch of the forward and of the backward behind it
+        self.drop_key = self._alloc("drop_key", (1,), torch.int64, dev)
+        self.drop_key.zero_()
+        self.drop = ()
         maxM = B * H0 * W0
         # per-level tensors
         for s in range(nl):
@@ -417,7 +423,7 @@ class TulipEngine:
             win, sft = effective_window(H, self.window, b % 2 == 1)
             if H % win[0] or W % win[1]:
                 raise NotImplementedError(f"token grid {H}x{W} not divisible by window {win}")
-            sp = BlockSpec(prefix, H, W, C, m.num_heads[s], b % 2 == 1, rate, win, sft)
+            sp = BlockSpec(prefix, H, W, C, m.num_heads[s], b % 2 == 1, rate, win, sft, idx=len(self.blocks))
             if rate > 0.0:
                 sp.slot = slot
                 slot += 2
@@ -434,6 +440,12 @@ class TulipEngine:
             self.dec_blocks.append([mk(f"layers_up.{i}.blocks.{b}", s, b, mods[b].drop_path_rate)
                                     for b in range(m.depths[s])])
         self.n_drop_slots = slot
+        # element dropout (nn.Dropout modules of the model): per block (attn_drop, proj_drop, mlp.drop1, mlp.drop2), engine order
+        self._drop_mods = []
+        for sp in self.blocks:
+            blk = m.get_submodule(sp.prefix)
+            self._drop_mods.append((blk.attn.attn_drop, blk.attn.proj_drop, blk.mlp.drop1, blk.mlp.drop2))
+        self._drop = ()
         self._keep = None
         self._pending = []        # weight-gradient launches queued for the side stream
         self._side_dirty = False
@@ -638,6 +650,8 @@ class TulipEngine:
         return ok
 
     def _fused_bwd(self, sp: BlockSpec, B: int) -> bool:
+        if self._dblock(sp):
+            return False
         return ((self.fuse_block96_bwd and self._fusable96(sp)) or (self.fuse_wide_bwd and self._fusable_wide(sp, B))
                 or self._fusable_deep(sp, B))
 
@@ -647,8 +661,35 @@ class TulipEngine:
     _tail_fused = False
 
     def _unfused(self, sp: BlockSpec, B: int) -> bool:
+        if self._dblock(sp):
+            return True
         return not ((self.fuse_wide and self._fusable_wide(sp, B)) or (self.fuse_block96 and self._fusable96(sp))
                     or self._fusable_deep(sp, B))
+
+    # ------------------------------------------------------------------ element dropout
+    # A site is active iff its nn.Dropout has p > 0 and is in training mode (the torch rule: model.eval() followed by switching the
+    # Dropout modules back to train() -- MC dropout -- activates them, DropPath follows model.training alone).  A block with an
+    # active site runs the unfused launch sequence both ways; every other block keeps its route.
+    def dropout_state(self) -> tuple:
+        """() when no site is active, else (pos_drop p, ((attn, proj, drop1, drop2) p per block)) with 0.0 for inactive sites"""
+        act = lambda d: float(d.p) if (d.training and d.p > 0.0) else 0.0
+        blocks = tuple(tuple(act(d) for d in mods) for mods in self._drop_mods)
+        pos = act(self.model.pos_drop)
+        if pos == 0.0 and not any(any(b) for b in blocks):
+            return ()
+        return (pos, blocks)
+
+    def _dblock(self, sp: BlockSpec) -> bool:
+        return bool(self._drop) and any(self._drop[1][sp.idx])
+
+    def _dp(self, sp: BlockSpec, kind: int) -> float:
+        """p of the block's site `kind` (0 attn_drop, 1 proj_drop, 2 drop1, 3 drop2), 0.0 if inactive"""
+        return self._drop[1][sp.idx][kind] if self._drop else 0.0
+
+    def _dkw(self, P: Plan, sp: Optional[BlockSpec], kind: int) -> dict:
+        site = 0 if sp is None else 1 + 4 * sp.idx + kind
+        p = self._drop[0] if sp is None else self._dp(sp, kind)
+        return dict(key=P.drop_key, seed=self._drop_seed, site=site, p=p)
 
     def _gemm_resid_ln(self, A, Wt, M, N, K, *, lda, ldb, bias, out, aux, rowscale, tok, ln, out2=None):
         """Linear + DropPath residual (EPI_RESID_F32) followed by a LayerNorm of its output rows, ln = (gamma, beta, xn, mean,
@@ -677,8 +718,9 @@ class TulipEngine:
         p = sp.prefix
         B, C, nh = P.B, sp.C, sp.nh
         M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
-        wide = self.fuse_wide and self._fusable_wide(sp, B)
-        if self._fusable_deep(sp, B):
+        drop = self._dblock(sp)                    # element dropout active in this block: the launch sequence below
+        wide = self.fuse_wide and self._fusable_wide(sp, B) and not drop
+        if self._fusable_deep(sp, B) and not drop:
             # four sliced launches (csrc/swind.hip: by heads, by output channels, by hidden channels, by output channels); same
             # tensors as the sequence
             self._join_pack(p)
@@ -700,7 +742,7 @@ class TulipEngine:
                 drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), B=B, H=sp.H, W=sp.W,
                 shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, B), eps=self.eps)
             return
-        if wide or (self.fuse_block96 and self._fusable96(sp)):
+        if wide or (self.fuse_block96 and self._fusable96(sp) and not drop):
             # the whole block in one launch (csrc/swin96.hip, csrc/swinw.hip); writes the same tensors as the sequence below
             if wide:
                 self._join_pack(p)                 # the fragment-major weight copies being rewritten beside the forward
@@ -738,6 +780,9 @@ class TulipEngine:
                               P[p + ".mean1"], P[p + ".rstd1"], M, C, self.eps)
         self._gemm(P[p + ".xn1"], W_.p16(p + ".attn.qkv.weight"), M, 3 * C, C, lda=C, ldb=C, epi=EPI_BF16,
                  bias=W_.p32(p + ".attn.qkv.bias"), out=P[p + ".qkv"])
+        if drop:
+            self._block_fwd_drop(P, sp, xin, xout, out_bf16, next_sp)
+            return
         ops.window_attn_fwd(P[p + ".qkv"], W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, P[p + ".o"],
                             B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp))
         self._gemm_resid_ln(P[p + ".o"], W_.p16(p + ".attn.proj.weight"), M, C, C, lda=C, ldb=C,
@@ -757,6 +802,52 @@ class TulipEngine:
         self._gemm(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd, epi=EPI_RESID_F32,
                  bias=W_.p32(p + ".mlp.fc2.bias"), out=xout, aux=P[p + ".x1"], ldaux=C,
                  rowscale=self._ds(P, sp, 1), rows_per_sample=tok, out2=out_bf16, ldo2=C if out_bf16 is not None else 0)
+
+    def _block_fwd_drop(self, P: Plan, sp: BlockSpec, xin, xout, out_bf16, next_sp):
+        """The rest of an unfused block's forward (behind the qkv GEMM) with its active element-dropout sites: attn_drop in the
+        attention kernel, proj_drop / drop2 as a plain fp32 Linear output + tulip_dropout_resid_ln (mask, DropPath scale, residual,
+        bf16 copy and the LayerNorm behind it), drop1 in place on the GELU output that fc2 and its weight gradient read."""
+        W_ = self.params
+        p = sp.prefix
+        B, C, nh = P.B, sp.C, sp.nh
+        M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
+        if self._dp(sp, 0):
+            ops.window_attn_fwd_drop(P[p + ".qkv"], W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, P[p + ".o"],
+                                     B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp), **self._dkw(P, sp, 0))
+        else:
+            ops.window_attn_fwd(P[p + ".qkv"], W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, P[p + ".o"],
+                                B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp))
+        ln2 = (W_.p32(p + ".norm2.weight"), W_.p32(p + ".norm2.bias"), P[p + ".xn2"], P[p + ".mean2"], P[p + ".rstd2"])
+        if self._dp(sp, 1):
+            self._gemm(P[p + ".o"], W_.p16(p + ".attn.proj.weight"), M, C, C, lda=C, ldb=C, epi=EPI_F32,
+                       bias=W_.p32(p + ".attn.proj.bias"), out=P[p + ".x1"])
+            ops.dropout_resid_ln(P[p + ".x1"], xin, self._ds(P, sp, 0), tok, P[p + ".x1"], None, ln2, self.eps, M, C,
+                                 **self._dkw(P, sp, 1))
+        else:
+            self._gemm_resid_ln(P[p + ".o"], W_.p16(p + ".attn.proj.weight"), M, C, C, lda=C, ldb=C,
+                                bias=W_.p32(p + ".attn.proj.bias"), out=P[p + ".x1"], aux=xin, rowscale=self._ds(P, sp, 0),
+                                tok=tok, ln=ln2)
+        self._gemm(P[p + ".xn2"], W_.p16(p + ".mlp.fc1.weight"), M, Hd, C, lda=C, ldb=C, epi=EPI_GELU_DUAL,
+                   bias=W_.p32(p + ".mlp.fc1.bias"), out=P[p + ".h"], out2=P[p + ".g"], ldo2=Hd)
+        if self._dp(sp, 2):
+            ops.dropout_scale(P[p + ".g"], True, M, Hd, **self._dkw(P, sp, 2))
+        ln_next = None
+        if next_sp is not None:
+            q = next_sp.prefix
+            ln_next = (W_.p32(q + ".norm1.weight"), W_.p32(q + ".norm1.bias"), P[q + ".xn1"], P[q + ".mean1"], P[q + ".rstd1"])
+        if self._dp(sp, 3):
+            self._gemm(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd, epi=EPI_F32,
+                       bias=W_.p32(p + ".mlp.fc2.bias"), out=xout)
+            ops.dropout_resid_ln(xout, P[p + ".x1"], self._ds(P, sp, 1), tok, xout, out_bf16, ln_next, self.eps, M, C,
+                                 **self._dkw(P, sp, 3))
+        elif ln_next is not None:
+            self._gemm_resid_ln(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd,
+                                bias=W_.p32(p + ".mlp.fc2.bias"), out=xout, aux=P[p + ".x1"], rowscale=self._ds(P, sp, 1),
+                                tok=tok, out2=out_bf16, ln=ln_next)
+        else:
+            self._gemm(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd, epi=EPI_RESID_F32,
+                       bias=W_.p32(p + ".mlp.fc2.bias"), out=xout, aux=P[p + ".x1"], ldaux=C,
+                       rowscale=self._ds(P, sp, 1), rows_per_sample=tok, out2=out_bf16, ldo2=C if out_bf16 is not None else 0)
 
     # run_forward(pack_on_side=True): the weight-copy refresh in two halves, [fork event, issued, joined] each.  Half 0 (the
     # encoder's wide blocks) is forked behind the forward's first kernel and joined in front of the first wide block; half 1
@@ -839,6 +930,8 @@ class TulipEngine:
         """Two consecutive C = 96 blocks as ONE launch (tulip_swin96_pair_fwd): the un-shifted block and the shifted block behind
         it, where the stage is one round of the chip (every workgroup resident: <= 256 tiles of 8 windows)."""
         if not (self.pair96 and self.fuse_block96 and self._fusable96(sp) and self._fusable96(nxt)):
+            return False
+        if self._dblock(sp) or self._dblock(nxt):
             return False
         if self._recomp96(sp) or self._recomp96(nxt) or (nxt.H, nxt.W) != (sp.H, sp.W):
             return False
@@ -947,6 +1040,14 @@ class TulipEngine:
         H0, W0 = self.grid
         kw = 8 if m.circular_padding else m.patch_size[1]
         pend, self._pending_draw = self._pending_draw, None
+        self._drop = P.drop = self.dropout_state()
+        if self._drop and self.attn_fp8 and any(b[0] for b in self._drop[1]):
+            raise NotImplementedError("tulip_amd: attn_drop (attn_drop_rate > 0 in training mode) is not built for the fp8 attention "
+                                      "scores (TULIP_ATTN_FP8=1)")
+        if self._drop:
+            # the step's mask counter: recorded in the plan's word (read by every dropout launch of this forward and its backward)
+            # and advanced -- by the DropPath draw behind it where there is one
+            ops.dropout_begin(self._drop_counter, P.drop_key, advance=pend is None)
         if pend is not None and pend[0] is not P:          # (drawn for another plan: a launch of its own)
             ops.drop_path_scales(*pend[1])
             pend = None
@@ -956,6 +1057,12 @@ class TulipEngine:
                             m.circular_padding, self.eps,
                             out_bf16=(P["dec0.cat"].data_ptr() + 2 * E) if nl > 1 else None, ld_bf16=2 * E,
                             draw=pend[1] if pend is not None else None)
+        if self._drop and self._drop[0]:
+            # pos_drop (tulip.py:705) on the embedding and on its bf16 copy, x_save[0] of the last skip concat
+            M0 = B * H0 * W0
+            ops.dropout_scale(P["enc0.in"], False, M0, E, **self._dkw(P, None, 0))
+            if nl > 1:
+                ops.dropout_scale(P["dec0.cat"].data_ptr() + 2 * E, True, M0, E, ld=2 * E, **self._dkw(P, None, 0))
         # three pieces: the encoder's wide blocks | the deep stages | the decoder's wide blocks
         two_packs = pack_on_side and W_.pk_active and nl > 2
         deep_pack = two_packs and nl >= 4 and any(w >= 768 for w in W_.pk_active)
@@ -1471,8 +1578,8 @@ class TulipEngine:
 
     def _mlp_cast(self, P: Plan, sp: BlockSpec):
         """What the producer of this block's incoming gradient should emit: (dyb_m, DropPath scale, tokens)."""
-        if self._fused_bwd(sp, P.B):
-            return None                     # the fused block backward forms its own operand from the fp32 gradient
+        if self._fused_bwd(sp, P.B) or self._dblock(sp):
+            return None                     # the fused block backward / a dropout block forms its own operand from the fp32 gradient
         return (P[sp.prefix + ".dyb_m"], self._ds(P, sp, 1), sp.H * sp.W)
 
     def _block_bwd(self, P: Plan, sp: BlockSpec, xin, dx, G, have_dyb=False, next_cast=None):
@@ -1485,7 +1592,8 @@ class TulipEngine:
         M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
         dxn, dO, dh, dqkv = P["t.dxn"], P["t.do"], P[p + ".dh"], P[p + ".dqkv"]
         dyb = P[p + ".dyb_m"]
-        if self._fusable_deep(sp, B):
+        drop = self._dblock(sp)
+        if self._fusable_deep(sp, B) and not drop:
             # csrc/swind.hip: fc2' + GELU' (by hidden channels) -> fc1' (by output channels) -> norm2' -> proj' + attention' (by heads)
             # -> qkv' (by output channels) -> norm1'; the LayerNorm backward launches are the sequence's own, fed one fp32 "slab"
             dn = P.scratch("deep.dxn", max(P.B * q.H * q.W * q.C for q in self.blocks if self._fusable_deep(q, P.B)))
@@ -1568,16 +1676,22 @@ class TulipEngine:
                 fn()
             return
         # ---- MLP branch (tulip.py:346-351)
-        if not have_dyb:
+        if drop and self._dp(sp, 3):                # drop2: bf16(dx * DropPath scale * mask / (1-p))
+            ops.dropout_cast(dx, dyb, M, C, self._ds(P, sp, 1), tok, **self._dkw(P, sp, 3))
+        elif not have_dyb or drop:
             ops.cast_f32_bf16(dx, dyb, M, C, self._ds(P, sp, 1), tok)
         self._gemm(dyb, W_.p16(p + ".mlp.fc2.weight"), M, Hd, C, lda=C, ldb=Hd, b_trans=True, epi=EPI_GELU_BWD, out=dh,
                  ldo=Hd, aux=P[p + ".h"], ldaux=Hd)
+        if drop and self._dp(sp, 2):                # drop1: the mask commutes with gelu'
+            ops.dropout_scale(dh, True, M, Hd, **self._dkw(P, sp, 2))
         self._release_deferred()
         self._wgrad(dyb, C, P[p + ".g"], Hd, C, Hd, M, G(p + ".mlp.fc2.weight"), G(p + ".mlp.fc2.bias"))
         self._dgrad_ln_bwd(P, dh, W_.p16(p + ".mlp.fc1.weight"), M, C, Hd, dxn,
                            (P[p + ".x1"], P[p + ".mean2"], P[p + ".rstd2"], W_.p32(p + ".norm2.weight"), dx, dx, M, C,
                             G(p + ".norm2.weight"), G(p + ".norm2.bias"), p + ".2"),
-                           dict(cast=(P[p + ".dyb_a"], self._ds(P, sp, 0), tok)))
+                           dict(cast=None if (drop and self._dp(sp, 1)) else (P[p + ".dyb_a"], self._ds(P, sp, 0), tok)))
+        if drop and self._dp(sp, 1):                # proj_drop
+            ops.dropout_cast(dx, P[p + ".dyb_a"], M, C, self._ds(P, sp, 0), tok, **self._dkw(P, sp, 1))
         self._wgrad(dh, Hd, P[p + ".xn2"], C, Hd, C, M, G(p + ".mlp.fc1.weight"), G(p + ".mlp.fc1.bias"))
         if sp.prefix in self.early_flush:
             # the last blocks of the backward: nothing is left to hide their weight gradients behind, so the MLP
@@ -1590,8 +1704,12 @@ class TulipEngine:
         self._wgrad(dyb, C, P[p + ".o"], C, C, C, M, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"))
         R = ops.window_attn_bwd_partial_rows(B, sp.H, sp.W, nh, sp.win)
         apart = P.scratch("apart." + p, R * nh * 256)
-        ops.window_attn_bwd(P[p + ".qkv"], dO, W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, dqkv,
-                            apart, B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp))
+        if drop and self._dp(sp, 0):
+            ops.window_attn_bwd_drop(P[p + ".qkv"], dO, W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, dqkv,
+                                     apart, B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp), **self._dkw(P, sp, 0))
+        else:
+            ops.window_attn_bwd(P[p + ".qkv"], dO, W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, dqkv,
+                                apart, B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp))
         self._fold_bias_table(P, p, apart, R, nh, G(p + ".attn.relative_position_bias_table"))
         self._dgrad_ln_bwd(P, dqkv, W_.p16(p + ".attn.qkv.weight"), M, C, 3 * C, dxn,
                            (xin, P[p + ".mean1"], P[p + ".rstd1"], W_.p32(p + ".norm1.weight"), dx, dx, M, C,
@@ -1677,6 +1795,7 @@ class TulipEngine:
         self.grad_overwrite = bool(overwrite)
         self.pack_at_end = bool(pack_at_end)
         self._gflat = gflat
+        self._drop = P.drop                           # the element-dropout sites of the forward this backward differentiates
         self.adam_apply = bool(apply_adamw and overwrite and self.adam_ctx is not None)
         if self._loss_final is not None:             # the loss read-out of run_forward(defer_loss_final=True): off the chain
             self._side(self._loss_final)
@@ -1898,6 +2017,8 @@ class TulipEngine:
         o0 = W_.offset["patch_embed.proj.weight"]
         rel = lambda n: 4 * (W_.offset[n] - o0)
         ep = P.embed_part_ptr
+        if self._drop and self._drop[0]:
+            ops.dropout_scale(P["enc0.dx"], False, B * H0 * W0, E, **self._dkw(P, None, 0))      # pos_drop
         ops.patch_embed_bwd(P.x_in, W_.p32("patch_embed.proj.weight"), W_.p32("patch_embed.proj.bias"),
                             W_.p32("patch_embed.norm.weight"), P["enc0.dx"], ep, ep + rel("patch_embed.proj.bias"),
                             ep + rel("patch_embed.norm.weight"), ep + rel("patch_embed.norm.bias"), B, m.in_chans,
@@ -1945,7 +2066,7 @@ class TulipEngine:
         # argument) and the number of draw slots
         key = key + (self.fuse_wide, self.fuse_wide_bwd, self.fuse_block96, self.fuse_block96_bwd, self.split_wide, self.split_wide_bwd,
                      self.fc1_grad_wide, self.fc1_grad96, self.recompute96, self.fuse_deep, self.fuse_tail_fwd, self.fuse_tail_bwd, self.fuse_glue, self.pair96, self.packed_gemm,
-                     int(self._drop_seed), int(self.n_drop_slots))
+                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state())
         ent = graphs.get(key)
         if not self.graph_module or ent is None:
             fn()

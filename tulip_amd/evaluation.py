@@ -213,17 +213,26 @@ def evaluate(data_loader, model, device, log_writer=None, args=None):
     return _finish(table, args, log_writer, "results.txt", ("mae", "chamfer_dist", "iou", "precision", "recall", "f1"))
 
 
+def enable_dropout(model):
+    """engine_upsampling.py:39-43: every nn.Dropout module back in train mode (MC dropout at evaluation time)"""
+    for m in model.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.train()
+
+
 @torch.no_grad()
 def MCdrop(data_loader, model, device, log_writer=None, args=None):
     """engine_upsampling.py:361-608: `num_mcdropout_iterations` forwards of the same input in tiles of 8, mean /
     std / threshold, then the evaluate pipeline with MCdrop's own gate; results_mcdrop.txt holds mae and
-    chamfer_dist only (:526-534).  Every reference configuration has dropout p=0, so the passes are identical
-    unless the model says otherwise."""
+    chamfer_dist only (:526-534).  As in the reference (:378-379) the model is put in eval mode and its Dropout modules back
+    in train mode (enable_dropout): with p > 0 (TULIP(drop_rate=..., attn_drop_rate=...)) every pass draws its own masks;
+    every reference configuration has p = 0, and then the passes are identical."""
     iteration, iteration_batch = args.num_mcdropout_iterations, 8
     assert iteration > iteration_batch                                                # :369
     ev = RangeEvaluator(args.dataset_select, args.img_size_low_res, args.img_size_high_res, args.log_transform,
                         args.grid_size, getattr(args, "keep_close_scan", False), True, device)
     model.eval()
+    enable_dropout(model)
     table = []
     for batch in data_loader:
         lo, hi = _samples(batch)

@@ -1,7 +1,9 @@
 """Batched inference: the eval / MC-dropout forward of TULIP.forward (tulip.py:702-735) captured
-once as a HIP graph and replayed.  `MCdrop` (engine_upsampling.py:411-419) tiles one input 8 times, so with every
-dropout probability at 0 (tulip.py:741-743) its forward is a deterministic B=8 batch: this is that launch sequence
-with the Python/launch overhead removed.  The graph reads `x` and writes `pred` in place."""
+once as a HIP graph and replayed.  `MCdrop` (engine_upsampling.py:411-419) tiles one input 8 times.  With every
+dropout probability at 0 (tulip.py:741-743), or the Dropout modules in eval mode, its forward is a deterministic B=8
+batch; with p > 0 and the Dropout modules in train mode (engine_upsampling.py:39-43 enable_dropout) every replay draws
+fresh masks (the mask counter lives on the device).  The Dropout flags in force at capture are part of the graph:
+changing them re-captures.  The graph reads `x` and writes `pred` in place."""
 from __future__ import annotations
 
 import torch
@@ -16,6 +18,7 @@ class GraphedForward:
         self.P = self.eng.plan(batch_size)
         self.B = batch_size
         self._graph = None
+        self._graph_drop = None
         self._side = torch.cuda.Stream(device=self.device)
 
     @property
@@ -44,7 +47,10 @@ class GraphedForward:
             self.eng.params.refresh_shadow()              # outside the graph: weights changed since capture
         elif self.eng.params.pack_dirty:
             self.eng.params.refresh_transposes()          # a Trainer stepped: its copies of the wide blocks' weights are due
+        if self._graph is not None and self._graph_drop != self.eng.dropout_state():
+            self._graph = None                            # Dropout modules switched train / eval since the capture
         if self._graph is None:
+            self._graph_drop = self.eng.dropout_state()
             self._forward()                               # load kernels / size lazy buffers outside capture
             torch.cuda.synchronize()
             self._side.wait_stream(torch.cuda.current_stream())

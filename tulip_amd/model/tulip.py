@@ -190,13 +190,12 @@ class TULIP(nn.Module):
         self.patch_size, self.in_chans = tuple(patch_size), in_chans
         self.log_transform, self.patch_unmerging = log_transform, patch_unmerging
         self.pixel_shuffle, self.circular_padding = pixel_shuffle, circular_padding
+        # element dropout (drop_rate: pos_drop, proj_drop, Mlp.drop1 / drop2; attn_drop_rate: attn_drop) -- the nn.Dropout modules
+        # hold p and the train / eval flag the engine reads at every forward (tulip_amd/engine.py, TulipEngine.dropout_state)
         self.pos_drop = nn.Dropout(p=drop_rate)
         if swin_v2:
             # the reference's V2 branch reads self.patch_embed before it exists (tulip.py:602 vs :571)
             raise AttributeError("'TULIP' object has no attribute 'patch_embed'")
-        if drop_rate != 0.0 or attn_drop_rate != 0.0:
-            raise NotImplementedError("tulip_amd: element dropout (drop_rate/attn_drop_rate) is 0 in every reference "
-                                      "configuration (tulip.py:741-743) and is not implemented in the HIP path")
         if not patch_norm:
             raise NotImplementedError("tulip_amd: patch_norm=False is not implemented (the patch-embedding kernel fuses the "
                                       "LayerNorm; every reference configuration keeps the default patch_norm=True)")

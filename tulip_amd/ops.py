@@ -378,6 +378,53 @@ def drop_path_scales(keep, scale, u_out, nslots, B, seed, counter):
                                              _p(counter), _stream()), "tulip_drop_path_scales")
 
 
+# ---- element dropout (include/tulip_hip.h, "Element dropout"); `key` is the step's counter word (int64 device tensor or address)
+def _seed(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def dropout_begin(counter, key, advance):
+    check(_lib.load().tulip_dropout_begin(_p(counter), _p(key), int(bool(advance)), _stream()), "tulip_dropout_begin")
+
+
+def dropout_mask(key, seed, site, p, n, out):
+    check(_lib.load().tulip_dropout_mask(_p(key), _seed(seed), int(site), float(p), int(n), _p(out), _stream()),
+          "tulip_dropout_mask")
+
+
+def dropout_scale(x, is_bf16, rows, cols, key, seed, site, p, ld=None):
+    check(_lib.load().tulip_dropout_scale(_p(x), int(bool(is_bf16)), rows, cols, cols if ld is None else ld, _p(key),
+                                          _seed(seed), int(site), float(p), _stream()), "tulip_dropout_scale")
+
+
+def dropout_resid_ln(y, aux, rowscale, rows_per_sample, out, out_bf16, ln, eps, rows, C, key, seed, site, p):
+    """ln = (gamma, beta, xn, mean, rstd) or None"""
+    g, b, xn, mean, rstd = ln if ln is not None else (None,) * 5
+    check(_lib.load().tulip_dropout_resid_ln(_p(y), _p(aux), _p(rowscale), rows_per_sample, _p(out), _p(out_bf16), _p(g),
+                                             _p(b), _p(xn), _p(mean), _p(rstd), float(eps), rows, C, _p(key), _seed(seed),
+                                             int(site), float(p), _stream()), "tulip_dropout_resid_ln")
+
+
+def dropout_cast(dx, y, rows, cols, rowscale, rows_per_sample, key, seed, site, p):
+    check(_lib.load().tulip_dropout_cast(_p(dx), _p(y), rows, cols, _p(rowscale), rows_per_sample, _p(key), _seed(seed),
+                                         int(site), float(p), _stream()), "tulip_dropout_cast")
+
+
+def window_attn_fwd_drop(qkv, bias_table, rel_index, out, B, H, W, C, nh, win, shift, masked, key, seed, site, p):
+    rc = _lib.load().tulip_window_attn_fwd_drop(_p(qkv), _p(bias_table), _p(rel_index), _p(out), B, H, W, C, nh, win[0],
+                                                win[1], shift[0], shift[1], int(masked), _p(key), _seed(seed), int(site),
+                                                float(p), _stream())
+    check(rc, "tulip_window_attn_fwd_drop")
+
+
+def window_attn_bwd_drop(qkv, dout, bias_table, rel_index, dqkv, dbias_dense, B, H, W, C, nh, win, shift, masked, key, seed,
+                         site, p):
+    rc = _lib.load().tulip_window_attn_bwd_drop(_p(qkv), _p(dout), _p(bias_table), _p(rel_index), _p(dqkv),
+                                                _p(dbias_dense), B, H, W, C, nh, win[0], win[1], shift[0], shift[1],
+                                                int(masked), _p(key), _seed(seed), int(site), float(p), _stream())
+    check(rc, "tulip_window_attn_bwd_drop")
+
+
 def kitti_range_map(points, n, rows, cols, ang_start_y, ang_res_y, ang_res_x, max_range, min_range, winner, out):
     check(_lib.load().tulip_kitti_range_map(_p(points), n, rows, cols, float(ang_start_y), float(ang_res_y),
                                             float(ang_res_x), float(max_range), float(min_range), _p(winner), _p(out),

@@ -97,6 +97,9 @@ class Trainer:
         if exchange not in ("allreduce", "sharded"):
             raise ValueError("exchange must be 'allreduce' or 'sharded'")
         self.exchange = exchange if self.segmented else "allreduce"
+        if self.exchange == "sharded" and (model.drop_rate > 0.0 or model.attn_drop_rate > 0.0):
+            raise ValueError("exchange='sharded' with element dropout (drop_rate / attn_drop_rate > 0) is not supported: "
+                             "use exchange='allreduce'")
         if self.exchange == "sharded":
             if track_grad_norm or grad_dtype != "fp32" or self.accum_iter != 1:
                 raise ValueError("exchange='sharded': fp32 gradients, no gradient-norm read-out, accum_iter == 1")
@@ -108,6 +111,7 @@ class Trainer:
         # encoder stage's group -- so a bucket's weights are dead once the bucket's hook has fired)
         self._segments = None     # {is_update_step: [(CUDAGraph, tag or None)]}
         self._pack_epoch = -1
+        self._seg_drop = None        # the element-dropout sites active when the step was captured (TulipEngine.dropout_state)
         # the fragment-major weight copies of the fused wide blocks (one ~25-us launch) are rewritten at the START of the
         # next step, beside the forward's first kernels, instead of on the chain behind AdamW
         self.pack_at_step_start = True
@@ -632,6 +636,8 @@ class Trainer:
             return self.P.losses
         if self._segments is not None and self._pack_epoch != self.eng.params.pack_epoch:
             self._segments = None       # another plan activated the weight copies of a width this capture does not rewrite
+        if self._segments is not None and self._seg_drop != self.eng.dropout_state():
+            self._segments = None       # Dropout modules switched train / eval: another launch sequence
         if self._segments is None:
             # load every kernel once outside capture, without touching parameters, optimizer state, the gradients of an
             # open accumulation window or the DropPath stream (the pass below accumulates into g and draws once)
@@ -652,6 +658,7 @@ class Trainer:
             del keep_g
             torch.cuda.synchronize()
             self._pack_epoch = self.eng.params.pack_epoch
+            self._seg_drop = self.eng.dropout_state()
             try:
                 self._segments = {True: self._capture(True)}
                 if self.accum_iter > 1:

@@ -88,7 +88,9 @@ int tulip_gemm_bf16(const void* A, int lda, int a_trans, const void* B, int ldb,
 /* Up to TULIP_REDUCE_REGIONS_MAX row reductions in one launch:  out[i] (+)= sum_{s<rows} partials[s*stride + i],
  * i < n (n, stride multiples of 4).  With scatter_index != NULL the region is the dense [scatter_nh][scatter_len]
  * relative-position-bias gradient and its sums are added to out[scatter_index[ij]*scatter_nh + h] instead
- * (tulip.py:304-308 backwards; one launch, deterministic: no atomics). */
+ * (tulip.py:304-308 backwards; deterministic, no atomics, for scatter_len 256 / 1024 / 4096 -- the 16- / 32- / 64-token
+ * windows; 1024 / 4096 take one more launch, one workgroup per head; other lengths add atomically).  A scatter region
+ * never takes the AdamW step. */
 #define TULIP_REDUCE_REGIONS_MAX 48
 typedef struct tulip_reduce_region {
     const float* partials; float* out;
@@ -255,11 +257,16 @@ int tulip_patch_embed_bwd_blocks(int ntok);
 /* bit 3, tulip_swinw_block_fwd / _bwd (+ split forms) only: skip the L2 warm-up at the head of the launch (below; measurement
  * and the bit-compare test only, results are identical either way) */
 #define TULIP_BLOCK_NO_WARM 8
+/* Shifted-window attention core on the [B*H*W][3C] qkv rows: windows of L = wh*ww tokens, L in {16, 32, 64} (2x8 / 1x16;
+ * 4x8, 2x16, 1x32; 8x8, 4x16, 2x32, 1x64), head dim C/nh in {16, 32}, rel_index the module's [L][L] index.  Any other L,
+ * or `masked` bit 1 (fp8 scores) with L != 16, returns TULIP_ERR_ARG before anything is launched. */
 int tulip_window_attn_fwd(const uint16_t* qkv, const float* bias_table, const int32_t* rel_index, uint16_t* out, int B,
                           int H, int W, int C, int nh, int wh, int ww, int sh, int sw, int masked, hipStream_t stream);
 /* dqkv from dout.  d(bias) leaves as R = tulip_window_attn_bwd_partial_rows(...) partial rows per head:
- * dbias_partials[(j*nh + h)*256 + i*16 + k], j < R  ==  a [R][nh*256] matrix whose column sums are the dense
- * [nh][16][16] gradient (fold + scatter into the table: tulip_reduce_rows_multi with scatter_index). */
+ * dbias_partials[(j*nh + h)*L*L + i*L + k], j < R  ==  a [R][nh*L*L] matrix whose column sums are the dense
+ * [nh][L][L] gradient (fold + scatter into the table: tulip_reduce_rows_multi with scatter_index, scatter_len L*L).
+ * L = 32 / 64: R <= max(1, 512 / nh), so the partial buffer R*nh*L*L floats is at most 2 MiB (L = 32) / 8 MiB (L = 64)
+ * for nh <= 512. */
 int tulip_window_attn_bwd(const uint16_t* qkv, const uint16_t* dout, const float* bias_table, const int32_t* rel_index,
                           uint16_t* dqkv, float* dbias_partials, int B, int H, int W, int C, int nh, int wh, int ww,
                           int sh, int sw, int masked, hipStream_t stream);
@@ -381,8 +388,9 @@ int tulip_drop_path_scales(const float* keep, float* scale, float* u_out, int ns
  * read through the pointer by every dropout launch of that forward and of its backward, so graph replays draw fresh masks;
  * site: 0 = pos_drop, block i (engine order) 1 + 4 i + {0 attn_drop, 1 proj_drop, 2 mlp.drop1, 3 mlp.drop2};
  * index: row * cols + c over natural token rows (pos_drop, proj_drop, drop2: cols = C; drop1: cols = hidden), and for
- * attn_drop ((((b * nWy + wy) * nWx + wx) * nh + head) * 16 + q) * 16 + k, (wy, wx) the window of the rolled image, q / k the
- * in-window slots i * ww + j -- the flattening of the reference's [B * nW, nh, N, N] probability tensor.  p in [0, 1). */
+ * attn_drop ((((b * nWy + wy) * nWx + wx) * nh + head) * L + q) * L + k, L = wh * ww the window's tokens, (wy, wx) the window of
+ * the rolled image, q / k the in-window slots i * ww + j -- the flattening of the reference's [B * nW, nh, N, N] probability
+ * tensor.  p in [0, 1). */
 /* *key_out = *counter; advance != 0: *counter += 1 (a forward whose DropPath draw does not advance it already) */
 int tulip_dropout_begin(uint64_t* counter, uint64_t* key_out, int advance, hipStream_t stream);
 /* mask read-out: out[i] = kept(i) ? scale : 0, i < n (fp32) */

@@ -381,6 +381,49 @@ extern "C" int tulip_reduce_rows2(const float* part0, int64_t stride0, float* ou
     return reduce_rows_impl(part0, stride0, out0, n0, part1, stride1, out1, n1, nrows, 0, stream);
 }
 
+// The deterministic scatter of a dense [nh][LL] bias-gradient region for LL = 1024 / 4096 (32- / 64-token windows), where a
+// head's sums span more columns than one reduce_rows_multi workgroup folds: one workgroup per head folds the head's LL
+// columns over the region's rows (row order) into LDS, then thread e adds the pairs of table entry e in index order -- the
+// LL == 256 path of reduce_rows_multi_kernel at a larger size (LDS broadcast reads: LL per entry).
+__global__ __launch_bounds__(256) void scatter_bias_kernel(const MultiRegion r) {
+    __shared__ float dense[4096];
+    __shared__ int sidx[4096];
+    __shared__ int nent;
+    const int h = blockIdx.x, LL = r.LL;
+    if (threadIdx.x == 0) nent = 0;
+    __syncthreads();
+    for (int c = threadIdx.x; c < LL / 4; c += 256) {
+        const float* base = r.part + (int64_t)h * LL + c * 4;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int s = 0; s < r.rows; ++s) {
+            const float4 v = *(const float4*)(base + (int64_t)s * r.stride);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        *(float4*)(dense + c * 4) = acc;
+    }
+    int mx = -1;
+    for (int ij = threadIdx.x; ij < LL; ij += 256) {
+        sidx[ij] = r.scatter[ij];
+        mx = max(mx, sidx[ij]);
+    }
+    atomicMax(&nent, mx + 1);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nent; e += 256) {
+        float s = 0.f;
+        bool any = false;
+#pragma unroll 8
+        for (int ij = 0; ij < LL; ++ij) {
+            const bool mine = sidx[ij] == e;
+            s += mine ? dense[ij] : 0.f;
+            any |= mine;
+        }
+        if (any) {
+            if (r.overwrite) r.out[e * r.nh + h] = s;
+            else r.out[e * r.nh + h] += s;
+        }
+    }
+}
+
 extern "C" int tulip_reduce_rows_multi(const tulip_reduce_region* regions, int n, hipStream_t stream) {
     return tulip_reduce_rows_multi_adamw(regions, n, nullptr, stream);
 }
@@ -396,6 +439,8 @@ extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions,
                 : AdamRef{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     R.n = 0;
     int blocks = 0;
+    MultiRegion wide[TULIP_REDUCE_REGIONS_MAX];     // scatter regions with LL = 1024 / 4096: scatter_bias_kernel
+    int nwide = 0;
     for (int i = 0; i < n; ++i) {
         const tulip_reduce_region& g = regions[i];
         if (g.n <= 0 || g.rows <= 0) continue;
@@ -408,6 +453,11 @@ extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions,
         // the step is taken only where the sum IS the gradient: an overwrite region without a scatter, optimizer buffers given
         if (g.adamw && (!adam || !g.overwrite || g.scatter_index)) return TULIP_ERR_ARG;
         r.adam = g.adamw ? 1 : 0;
+        if (g.scatter_index && (g.scatter_len == 1024 || g.scatter_len == 4096)) {
+            wide[nwide++] = r;
+            --R.n;
+            continue;
+        }
         // one thread per float4 column when there are few rows; otherwise spread the rows over 2..16 row lanes until
         // the region has enough workgroups to hide the strided loads (32-row slabs of a 37k-column weight gradient
         // took 50-80 us with one thread per column)
@@ -418,9 +468,14 @@ extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions,
         const int ct = 256 / r.rl;
         blocks += (int)((r.n4 + ct - 1) / ct);
     }
-    if (blocks == 0) return TULIP_OK;
-    hipLaunchKernelGGL(reduce_rows_multi_kernel, dim3(blocks), dim3(256), 0, stream, R);
-    TULIP_CHECK_LAUNCH();
+    if (blocks > 0) {
+        hipLaunchKernelGGL(reduce_rows_multi_kernel, dim3(blocks), dim3(256), 0, stream, R);
+        TULIP_CHECK_LAUNCH();
+    }
+    for (int i = 0; i < nwide; ++i) {
+        hipLaunchKernelGGL(scatter_bias_kernel, dim3(wide[i].nh), dim3(256), 0, stream, wide[i]);
+        TULIP_CHECK_LAUNCH();
+    }
     return TULIP_OK;
 }
 

@@ -56,7 +56,8 @@ def multiplier(seed: int, counter: int, site_id: int, p: float, index) -> np.nda
 
 
 def attn_index(B: int, H: int, W: int, nh: int, win) -> np.ndarray:
-    """[B * nW, nh, 16, 16] -> flat index of the reference's attention-probability tensor (its own flattening)"""
+    """[B * nW, nh, L, L] (L = wh * ww) -> flat index of the reference's attention-probability tensor (its own
+    flattening): ((window * nh + head) * L + q) * L + k"""
     wh, ww = win
     n = B * (H // wh) * (W // ww) * nh * (wh * ww) ** 2
     return np.arange(n, dtype=np.uint64).reshape(B * (H // wh) * (W // ww), nh, wh * ww, wh * ww)

@@ -404,8 +404,11 @@ class TulipEngine:
             raise NotImplementedError("tulip_amd fused head supports upscale_factor == 4 (every BASELINE config)")
         ws = m.window_size if isinstance(m.window_size, (tuple, list)) else (m.window_size, m.window_size)
         self.window = (int(ws[0]), int(ws[1]))
-        if self.window[0] * self.window[1] != 16:
-            raise NotImplementedError("tulip_amd attention kernel supports 16-token windows (window_size 2 8)")
+        # tokens per window: the attention kernels cover L = 16 (fused block kernels, fp8 scores) and L = 32 / 64
+        self.win_len = self.window[0] * self.window[1]
+        if self.win_len not in (16, 32, 64):
+            raise NotImplementedError(f"tulip_amd attention kernels support windows of 16, 32 or 64 tokens (window_size h w "
+                                      f"with h * w in {{16, 32, 64}}); got window_size {self.window}, {self.win_len} tokens")
         ph, pw = m.patch_size
         if m.img_size[0] % ph or m.img_size[1] % pw:
             raise NotImplementedError("img_size must be divisible by patch_size")
@@ -600,6 +603,11 @@ class TulipEngine:
     # everything else unchanged); the backward differentiates exactly that function (it multiplies dS with the rounded
     # q, k).  Off by default: the reference computes the scores from bf16 / fp16 operands.
     attn_fp8 = knobs.is_one("TULIP_ATTN_FP8")
+
+    def check_attn_fp8(self):
+        if self.attn_fp8 and self.win_len != 16:
+            raise NotImplementedError(f"tulip_amd: fp8 attention scores (TULIP_ATTN_FP8=1 / Trainer(attn_fp8=True)) are built for "
+                                      f"16-token windows only; this model's window {self.window} has {self.win_len} tokens")
 
     def _mask_arg(self, sp: BlockSpec, B: Optional[int] = None) -> int:
         """`masked` argument of the attention / block kernels: bit 0 shifted-window mask, bit 1 fp8 scores, bit 2 (fused
@@ -1028,6 +1036,7 @@ class TulipEngine:
         pack_on_side (Trainer): the fragment-major weight copies of the fused wide blocks are rewritten from the bf16
         shadow beside the forward's first kernels (side stream, joined in front of the first wide block) instead of on
         the chain behind AdamW."""
+        self.check_attn_fp8()
         m, W_ = self.model, self.params
         if W_.shadow_dirty:
             W_.refresh_shadow()
@@ -1339,16 +1348,17 @@ class TulipEngine:
         return self.adam_ctx if self.adam_apply else None
 
     def _fold_bias_table(self, P: Plan, tag: str, part, rows: int, nh: int, gtable):
-        """Relative-position-bias gradient of one block: partial rows [rows][nh*256] (dense (head, query, key) sums per
-        workgroup) -> table gradient [45][nh] through the relative-position index (tulip.py:304-308 backwards).  Two
-        steps, both deterministic: the dense fold runs with every other fold of the block (all columns in parallel);
-        the scatter of its [nh*256] result -- one workgroup per head adding the pairs of every table entry in index
-        order -- rides in the NEXT side launch (a region of one row), so no launch is added and no workgroup has to
+        """Relative-position-bias gradient of one block: partial rows [rows][nh*LL] (dense (head, query, key) sums per
+        workgroup, LL = L*L) -> table gradient [(2wh-1)(2ww-1)][nh] through the relative-position index (tulip.py:304-308
+        backwards).  Two steps, both deterministic: the dense fold runs with every other fold of the block (all columns
+        in parallel); the scatter of its [nh*LL] result -- one workgroup per head adding the pairs of every table entry in
+        index order -- rides in the NEXT side launch (a region of one row), so no launch is added and no workgroup has to
         pull a whole partial matrix through one CU."""
-        dense = P.scratch("apd." + tag, nh * 256)
-        self._fold(part, nh * 256, dense, nh * 256, rows, overwrite=True)
-        r = ops.reduce_region(dense, nh * 256, gtable, nh * 256, 1, overwrite=self.grad_overwrite, scatter_index=self._rel32,
-                              scatter_nh=nh, scatter_len=256)
+        LL = self.win_len * self.win_len
+        dense = P.scratch("apd." + tag, nh * LL)
+        self._fold(part, nh * LL, dense, nh * LL, rows, overwrite=True)
+        r = ops.reduce_region(dense, nh * LL, gtable, nh * LL, 1, overwrite=self.grad_overwrite, scatter_index=self._rel32,
+                              scatter_nh=nh, scatter_len=LL)
         if self.overlap_wgrad:
             self._pending.append(("s", r))
         else:
@@ -1598,7 +1608,7 @@ class TulipEngine:
             # -> qkv' (by output channels) -> norm1'; the LayerNorm backward launches are the sequence's own, fed one fp32 "slab"
             dn = P.scratch("deep.dxn", max(P.B * q.H * q.W * q.C for q in self.blocks if self._fusable_deep(q, P.B)))
             R = ops.swind_groups(C, B, sp.H, sp.W, sp.win)
-            apart = P.scratch("apart." + p, R * nh * 256)
+            apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
             wt = W_.p16t
             desc = dict(
                 dx=dx, x_in=xin, x1=P[p + ".x1"], qkv=P[p + ".qkv"], fc1_pre=P[p + ".h"], mean1=P[p + ".mean1"],
@@ -1637,7 +1647,7 @@ class TulipEngine:
                 raise ValueError("fused block backward: the cast scale must be per sample")
             R = ops.swinw_bwd_partial_rows(C, B, sp.H, sp.W) if wide else ops.swin96_bwd_partial_rows(B, sp.H, sp.W)
             ln1, ln2 = P.scratch("lnp." + p + ".1", R * 2 * C), P.scratch("lnp." + p + ".2", R * 2 * C)
-            apart = P.scratch("apart." + p, R * nh * 256)
+            apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
             xkw = {}
             if wide and self.split_wide_bwd and self._hgrad_wide(sp, B):
                 nb = ops.swinw_split_bytes(C, B, sp.H, sp.W)       # two workgroups per window (tulip_swinw_block_bwd_split)
@@ -1703,7 +1713,7 @@ class TulipEngine:
                  ldo=C)
         self._wgrad(dyb, C, P[p + ".o"], C, C, C, M, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"))
         R = ops.window_attn_bwd_partial_rows(B, sp.H, sp.W, nh, sp.win)
-        apart = P.scratch("apart." + p, R * nh * 256)
+        apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
         if drop and self._dp(sp, 0):
             ops.window_attn_bwd_drop(P[p + ".qkv"], dO, W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, dqkv,
                                      apart, B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp), **self._dkw(P, sp, 0))

@@ -58,6 +58,7 @@ class Trainer:
         self.eng = model.engine()
         if attn_fp8 is not None:      # BASELINE configs[4]: attention scores from e4m3 q, k (default: env TULIP_ATTN_FP8, off)
             self.eng.attn_fp8 = bool(attn_fp8)
+        self.eng.check_attn_fp8()
         self.eng.bind(device)
         self.P = self.eng.plan(batch_size)
         W = self.eng.params

@@ -231,7 +231,8 @@ int tulip_patch_embed_fwd_draw(const float* img, const float* w, const float* b,
                                float eps, uint16_t* out_bf16, int ld_bf16, const tulip_drop_draw* draw, hipStream_t stream);
 /* parameter gradients of the above (the input image needs no gradient).  partial_stride > 0: dw/db/dgamma/
  * dbeta point into row 0 of a [tulip_patch_embed_bwd_blocks(ntok)][partial_stride] partial buffer (plain
- * stores; fold with tulip_reduce_rows2); partial_stride == 0: accumulate atomically into the gradients. */
+ * stores; fold with tulip_reduce_rows2); partial_stride == 0: accumulate atomically into the gradients.
+ * Partial rows cover Cin * p0 * kw <= 16 taps at any E, and up to 32 taps (Cin 2 .. 4) at E = 48 / 96. */
 int tulip_patch_embed_bwd(const float* img, const float* w, const float* b, const float* gamma, const float* dout,
                           float* dw, float* db, float* dgamma, float* dbeta, int B, int Cin, int Hin, int Win, int E,
                           int p0, int p1, int kw, int circular, float eps, int partial_stride, hipStream_t stream);
@@ -281,10 +282,15 @@ int tulip_cast_flat(const float* x, uint16_t* y, int64_t n, hipStream_t stream);
 int tulip_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t stream);
 
 /* Fused head (tulip.py:724-731): conv1x1 E->16E (+bias), LeakyReLU(0.01), PixelShuffle(4),
- * conv1x1 E->1 (no bias); xn is norm_up's bf16 output [B*H*W][E]; pred is (B,1,4H,4W) fp32.  The
- * (B,16E,H,W) intermediate (100 MB at B=8) is never materialised.  upscale factor 4, in_chans 1. */
+ * conv1x1 E->in_chans (no bias, wd [in_chans][E]); xn is norm_up's bf16 output [B*H*W][E]; pred is (B,in_chans,4H,4W)
+ * fp32.  The (B,16E,H,W) intermediate (100 MB at B=8) is never materialised.  upscale factor 4.
+ * Every head entry point has a _c form with a trailing int in_chans (1 .. 4; anything else: TULIP_ERR_ARG); the form
+ * without it is in_chans 1.  With in_chans > 1 the decoder_pred partial rows are [row][in_chans][128] and the L1
+ * gradient divides by numel = in_chans * 16 * B*H*W. */
 int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred, int B, int H,
                    int W, int E, hipStream_t stream);
+int tulip_tail_fwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred, int B, int H,
+                     int W, int E, hipStream_t stream, int in_chans);
 /* backward of the head w.r.t. the expand pre-activation: dz[B*H*W][16E] (bf16), and decoder_pred's weight
  * gradient as ceil(B*H*W/32) partial rows dwd_partials[row][128] (first E valid; fold with
  * tulip_reduce_rows2).  target == NULL: dpred is the upstream gradient of pred.  target != NULL: dpred is the
@@ -293,6 +299,9 @@ int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const float* be, cons
 int tulip_tail_bwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                    uint16_t* dz, float* dwd_partials, int B, int H, int W, int E, const float* target,
                    const float* gscale_dev, float gscale, hipStream_t stream);
+int tulip_tail_bwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                     uint16_t* dz, float* dwd_partials, int B, int H, int W, int E, const float* target,
+                     const float* gscale_dev, float gscale, hipStream_t stream, int in_chans);
 /* The same backward WITHOUT the (B,16E,H,W) gradient tensor (100 MB at batch 8, written once and read twice): both
  * consumers recompute it.  tulip_tail_bwd_dgrad (the chain): dxn[B*H*W][E] (bf16) = dz . We, the input of norm_up's
  * backward (autograd of tulip.py:724-731), and the decoder_pred partial rows exactly as tulip_tail_bwd writes them.
@@ -303,6 +312,9 @@ int tulip_tail_fused_bwd_supported(int E);
 int tulip_tail_bwd_dgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                          uint16_t* dxn, float* dwd_partials, int B, int H, int W, int E, const float* target,
                          const float* gscale_dev, float gscale, hipStream_t stream);
+int tulip_tail_bwd_dgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                           uint16_t* dxn, float* dwd_partials, int B, int H, int W, int E, const float* target,
+                           const float* gscale_dev, float gscale, hipStream_t stream, int in_chans);
 /* tulip_tail_bwd_dgrad with norm_up's backward (autograd of tulip.py:720) in its epilogue: instead of dxn it writes what
  * tulip_layernorm_bwd would -- dx[B*H*W][E] (fp32, overwritten), optionally dx_bf16 = bf16(dx * cast_rowscale[token /
  * cast_rows_per_sample]) and ceil(B*H*W/32) partial rows ln_partials[row][2E] = [dgamma | dbeta] (fold with
@@ -312,6 +324,11 @@ int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, const float*
                             float gscale, const float* x, const float* mean, const float* rstd, const float* gamma,
                             float* dx, uint16_t* dx_bf16, const float* cast_rowscale, int cast_rows_per_sample,
                             float* ln_partials, hipStream_t stream);
+int tulip_tail_bwd_dgrad_ln_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                              float* dwd_partials, int B, int H, int W, int E, const float* target, const float* gscale_dev,
+                              float gscale, const float* x, const float* mean, const float* rstd, const float* gamma,
+                              float* dx, uint16_t* dx_bf16, const float* cast_rowscale, int cast_rows_per_sample,
+                              float* ln_partials, hipStream_t stream, int in_chans);
 /* tulip_tail_fwd with norm_up (tulip.py:720: LayerNorm(E) of the fp32 rows x, eps) in front -- xn / mean / rstd are written
  * for the backward -- and, when loss_partials != NULL, the partial sums of forward_loss (tulip.py:690-700) behind it:
  * loss_partials[2*wg] = sum |pred - target|, [2*wg+1] = sum |expm1(pred) - expm1(target)| (log_transform) over the
@@ -319,12 +336,19 @@ int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, const float*
 int tulip_tail_fwd_ln(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
                       float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred, const float* target,
                       float* loss_partials, int log_transform, int B, int H, int W, int E, hipStream_t stream);
+int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+                        float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred, const float* target,
+                        float* loss_partials, int log_transform, int B, int H, int W, int E, hipStream_t stream,
+                        int in_chans);
 int tulip_l1_loss_final(const float* partials, float* losses, int nblocks, int64_t n, int log_transform,
                         hipStream_t stream);
 int tulip_tail_wgrad_splits(int B, int H, int W, int E);
 int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                      float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
                      const float* gscale_dev, float gscale, hipStream_t stream);
+int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                       float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
+                       const float* gscale_dev, float gscale, hipStream_t stream, int in_chans);
 
 
 /* The non-default decoder alternates PatchExpanding (tulip.py:126-140, patch_unmerging=False; P = 2, Cn = C/2) and
@@ -333,18 +357,26 @@ int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, co
  * TULIP_EPI_F32 into y [B*H*W][P*P*Cn] fp32; a fine token is a contiguous Cn-slice of a row of y, so the rearrange is
  * the OUTPUT addressing of these kernels.  fwd: LayerNorm of every slice -> out_bf16 (optional; fine-token order,
  * row pitch ld, e.g. the first half of a skip-concat buffer, tulip.py:715) and/or pred[fine token] =
- * sum_c dotw[c] * bf16(LayerNorm out)[c] (optional: decoder_pred, tulip.py:731, in_chans == 1, the (B,PH,PW,Cn)
- * tensor is never stored).  mean / rstd: [B*H*W*P*P] in the (coarse token, p) order of y.
+ * sum_c dotw[c] * bf16(LayerNorm out)[c] (optional: decoder_pred, tulip.py:731, the (B,PH,PW,Cn) tensor is never
+ * stored; the _c forms take a trailing in_chans 1 .. 4: dotw [in_chans][Cn], pred (B,in_chans,PH,PW), Cn <= 256 when
+ * in_chans > 1).  mean / rstd: [B*H*W*P*P] in the (coarse token, p) order of y.
  * bwd: upstream gradient either as bf16 rows dy_fine (fine-token order, row pitch ld) or, when dotw != NULL, as
  * dpred[fine token] (then d(LayerNorm out)[c] = dpred * dotw[c]) -> dy_nat = bf16 d(y) in y's layout (operand of the
  * Linear's dgrad / wgrad GEMMs) and tulip_expand_norm_bwd_partial_rows(...) partial rows of
- * [dgamma[Cn] | dbeta[Cn] | d(dotw)[Cn]] (stride 3*Cn; fold with tulip_reduce_rows_multi).  Cn % 4 == 0, Cn <= 768. */
+ * [dgamma[Cn] | dbeta[Cn] | d(dotw)[in_chans][Cn]] (stride (2 + in_chans)*Cn; fold with tulip_reduce_rows_multi).
+ * Cn % 4 == 0, Cn <= 768. */
 int tulip_expand_norm_fwd(const float* y, const float* gamma, const float* beta, uint16_t* out_bf16, int ld,
                           const float* dotw, float* pred, float* mean, float* rstd, int B, int H, int W, int P, int Cn,
                           float eps, hipStream_t stream);
 int tulip_expand_norm_bwd(const uint16_t* dy_fine, int ld, const float* dpred, const float* dotw, const float* y,
                           const float* mean, const float* rstd, const float* gamma, const float* beta, uint16_t* dy_nat,
                           float* partials, int B, int H, int W, int P, int Cn, hipStream_t stream);
+int tulip_expand_norm_fwd_c(const float* y, const float* gamma, const float* beta, uint16_t* out_bf16, int ld,
+                            const float* dotw, float* pred, float* mean, float* rstd, int B, int H, int W, int P, int Cn,
+                            float eps, hipStream_t stream, int in_chans);
+int tulip_expand_norm_bwd_c(const uint16_t* dy_fine, int ld, const float* dpred, const float* dotw, const float* y,
+                            const float* mean, const float* rstd, const float* gamma, const float* beta, uint16_t* dy_nat,
+                            float* partials, int B, int H, int W, int P, int Cn, hipStream_t stream, int in_chans);
 int tulip_expand_norm_bwd_partial_rows(int B, int H, int W, int P);
 
 /* forward_loss (tulip.py:690-700): losses[0]=mean|pred-target|, losses[1]=mean|expm1(pred)-expm1(target)|

@@ -149,6 +149,15 @@ SIGNATURES = {
     "tulip_expand_norm_fwd": [P, P, P, P, I, P, P, P, P, I, I, I, I, I, F, P],
     "tulip_expand_norm_bwd": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "tulip_expand_norm_bwd_partial_rows": [I, I, I, I],
+    # the head / FinalPatchExpanding entry points with a trailing in_chans (1 .. 4)
+    "tulip_tail_fwd_c": [P, P, P, P, P, I, I, I, I, P, I],
+    "tulip_tail_bwd_c": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I],
+    "tulip_tail_bwd_dgrad_c": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I],
+    "tulip_tail_bwd_dgrad_ln_c": [P, P, P, P, P, P, I, I, I, I, P, P, F, P, P, P, P, P, P, P, I, P, P, I],
+    "tulip_tail_fwd_ln_c": [P, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I],
+    "tulip_tail_wgrad_c": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I],
+    "tulip_expand_norm_fwd_c": [P, P, P, P, I, P, P, P, P, I, I, I, I, I, F, P, I],
+    "tulip_expand_norm_bwd_c": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I],
     "tulip_l1_loss_fwd": [P, P, P, P, L, I, P],
     "tulip_l1_loss_bwd": [P, P, P, F, P, L, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],

@@ -335,11 +335,12 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_kernel(const float* __res
     }
 }
 
-// Single-channel images with one-row patches (every range-image configuration of the reference: in_chans 1, patch
-// (1,4), KW = 8 taps with circular padding or 4 without): a tap is just a column offset, and a wave works on 4
-// consecutive tokens at once so that their loads / two LayerNorm reductions / stores are 4 independent chains (the
-// generic kernel spends most of its 30 us in per-tap index arithmetic and one dependent chain per token).
-template <int KW>
+// Images of CIN <= 4 channels with one-row patches (every range-image configuration of the reference: patch (1,4), KW = 8
+// taps per channel with circular padding or 4 without; CIN = 2 for [range, intensity]): a tap is just a column offset in
+// one of CIN image rows, and a wave works on 4 consecutive tokens at once so that their loads / two LayerNorm reductions /
+// stores are 4 independent chains (the generic kernel spends most of its 30 us in per-tap index arithmetic and one
+// dependent chain per token).
+template <int KW, int CIN>
 __global__ __launch_bounds__(256) void patch_embed_fwd_row_kernel(const float* __restrict__ img,
                                                                   const float* __restrict__ w, const float* __restrict__ bias,
                                                                   const float* __restrict__ gamma,
@@ -354,27 +355,40 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_row_kernel(const float* _
     const int c0 = lane, c1 = lane + 64;
     const bool v0 = c0 < g.E, v1 = c1 < g.E;
     const float invE = 1.0f / (float)g.E;
-    float w0[KW], w1[KW];
+    constexpr int T = CIN * KW;                                        // taps: t = ic * KW + k
+    float w0[T], w1[T];
 #pragma unroll
-    for (int t = 0; t < KW; ++t) {
-        w0[t] = v0 ? w[c0 * KW + t] : 0.f;
-        w1[t] = v1 ? w[c1 * KW + t] : 0.f;
+    for (int t = 0; t < T; ++t) {
+        w0[t] = v0 ? w[c0 * T + t] : 0.f;
+        w1[t] = v1 ? w[c1 * T + t] : 0.f;
     }
     const float b0 = v0 ? bias[c0] : 0.f, b1 = v1 ? bias[c1] : 0.f;
     const float ga0 = v0 ? gamma[c0] : 0.f, ga1 = v1 ? gamma[c1] : 0.f;
     const float be0 = v0 ? beta[c0] : 0.f, be1 = v1 ? beta[c1] : 0.f;
     for (int tok0 = wave * UNR; tok0 < ntok; tok0 += nwaves * UNR) {
-        float xt[UNR][KW];
+        float xt[UNR][T];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int tok = min(tok0 + u, ntok - 1);
             const int trow = fast_div(tok, g.Wo), wq = tok - trow * g.Wo;
-            const float* rowp = img + (size_t)trow * g.Win;                  // Cin == 1, p0 == 1: image row = b*Ho + h
+            if constexpr (CIN == 1) {
+                const float* rowp = img + (size_t)trow * g.Win;              // Cin == 1, p0 == 1: image row = b*Ho + h
 #pragma unroll
-            for (int k = 0; k < KW; ++k) {
-                int col = g.p1 * wq + k;
-                if (g.circular) { col -= 2; if (col < 0) col += g.Win; if (col >= g.Win) col -= g.Win; }
-                xt[u][k] = rowp[col];
+                for (int k = 0; k < KW; ++k) {
+                    int col = g.p1 * wq + k;
+                    if (g.circular) { col -= 2; if (col < 0) col += g.Win; if (col >= g.Win) col -= g.Win; }
+                    xt[u][k] = rowp[col];
+                }
+            } else {
+                const int b = fast_div(trow, g.Ho);                         // p0 == 1: channel ic's row = (b*CIN + ic)*Ho + h
+                const float* rowp = img + (size_t)(trow + b * (CIN - 1) * g.Ho) * g.Win;
+#pragma unroll
+                for (int k = 0; k < KW; ++k) {
+                    int col = g.p1 * wq + k;
+                    if (g.circular) { col -= 2; if (col < 0) col += g.Win; if (col >= g.Win) col -= g.Win; }
+#pragma unroll
+                    for (int ic = 0; ic < CIN; ++ic) xt[u][ic * KW + k] = rowp[(size_t)ic * g.Ho * g.Win + col];
+                }
             }
         }
         float a0[UNR], a1[UNR], mu[UNR], rs[UNR];
@@ -382,7 +396,7 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_row_kernel(const float* _
         for (int u = 0; u < UNR; ++u) {
             a0[u] = b0; a1[u] = b1;
 #pragma unroll
-            for (int k = 0; k < KW; ++k) { a0[u] += w0[k] * xt[u][k]; a1[u] += w1[k] * xt[u][k]; }
+            for (int k = 0; k < T; ++k) { a0[u] += w0[k] * xt[u][k]; a1[u] += w1[k] * xt[u][k]; }
             mu[u] = (v0 ? a0[u] : 0.f) + (v1 ? a1[u] : 0.f);
         }
 #pragma unroll
@@ -810,7 +824,7 @@ extern "C" int tulip_patch_embed_fwd_draw(const float* img, const float* w, cons
     if (!embed_geom(g, B, Cin, Hin, Win, E, p0, p1, kw, circular)) return TULIP_ERR_ARG;
     if (draw && (!draw->keep || !draw->scale || !draw->counter || draw->nslots <= 0 || draw->B <= 0)) return TULIP_ERR_ARG;
     const int ntok = g.B * g.Ho * g.Wo;
-    const bool row = g.Cin == 1 && g.p0 == 1 && g.taps == g.kw && (g.kw == 8 || g.kw == 4) && E <= 128 && ntok > 0;
+    const bool row = g.Cin >= 1 && g.Cin <= 4 && g.p0 == 1 && (g.kw == 8 || g.kw == 4) && E <= 128 && ntok > 0;
     DropDraw dd{nullptr, nullptr, nullptr, 0, 0, 0ull, nullptr};
     if (draw && row) {
         dd = DropDraw{draw->keep, draw->scale, draw->u_out, draw->nslots, draw->B, (unsigned long long)draw->seed,
@@ -824,12 +838,15 @@ extern "C" int tulip_patch_embed_fwd_draw(const float* img, const float* w, cons
     const int grid = std::min((ntok + 3) / 4, 256 * 8);
     if (row) {
         const int grid4 = std::min((ntok + 15) / 16, 256 * 2);   // 8 waves per CU, each amortises its weight loads
-        if (g.kw == 8)
-            hipLaunchKernelGGL(patch_embed_fwd_row_kernel<8>, dim3(grid4), dim3(256), 0, stream, img, w, b, gamma, beta,
-                               out, (bf16_t*)out_bf16, ld_bf16, g, eps, dd);
-        else
-            hipLaunchKernelGGL(patch_embed_fwd_row_kernel<4>, dim3(grid4), dim3(256), 0, stream, img, w, b, gamma, beta,
-                               out, (bf16_t*)out_bf16, ld_bf16, g, eps, dd);
+#define TULIP_PE_ROW(KW, CIN) hipLaunchKernelGGL((patch_embed_fwd_row_kernel<KW, CIN>), dim3(grid4), dim3(256), 0, stream, img, w, \
+                                                 b, gamma, beta, out, (bf16_t*)out_bf16, ld_bf16, g, eps, dd)
+#define TULIP_PE_ROW_C(KW) \
+        switch (g.Cin) { case 1: TULIP_PE_ROW(KW, 1); break; case 2: TULIP_PE_ROW(KW, 2); break; \
+                         case 3: TULIP_PE_ROW(KW, 3); break; default: TULIP_PE_ROW(KW, 4); break; }
+        if (g.kw == 8) { TULIP_PE_ROW_C(8) }
+        else { TULIP_PE_ROW_C(4) }
+#undef TULIP_PE_ROW_C
+#undef TULIP_PE_ROW
         TULIP_CHECK_LAUNCH();
         return TULIP_OK;
     }
@@ -853,13 +870,16 @@ extern "C" int tulip_patch_embed_bwd(const float* img, const float* w, const flo
     if (!embed_geom(g, B, Cin, Hin, Win, E, p0, p1, kw, circular)) return TULIP_ERR_ARG;
     const int ntok = g.B * g.Ho * g.Wo;
     if (ntok <= 0) return TULIP_OK;
-    if (partial_stride > 0 && g.taps > EMB_MAXT) return TULIP_ERR_ARG;
+    // partial rows past EMB_MAXT taps (in_chans 2 .. 4): the 16-lane form up to 32 taps, at E = 96 / 48
+    if (partial_stride > 0 && g.taps > EMB_MAXT && !(g.taps <= 32 && (E == 96 || E == 48))) return TULIP_ERR_ARG;
     const int grid = tulip_patch_embed_bwd_blocks(ntok);
-    if (partial_stride > 0 && g.taps <= EMB_MAXT && (E == 96 || E == 48)) {
+    if (partial_stride > 0 && g.taps <= 32 && (E == 96 || E == 48)) {
 #define TULIP_PE_BWD(CPL, TAPS) hipLaunchKernelGGL((patch_embed_bwd16_kernel<CPL, TAPS>), dim3(grid), dim3(256), 0, stream, \
                                                   img, w, b, gamma, dout, dw, db, dgamma, dbeta, g, eps, partial_stride)
         if (g.taps <= 8) { if (E == 96) TULIP_PE_BWD(6, 8); else TULIP_PE_BWD(3, 8); }
-        else { if (E == 96) TULIP_PE_BWD(6, 16); else TULIP_PE_BWD(3, 16); }
+        else if (g.taps <= 16) { if (E == 96) TULIP_PE_BWD(6, 16); else TULIP_PE_BWD(3, 16); }
+        else if (g.taps <= 24) { if (E == 96) TULIP_PE_BWD(6, 24); else TULIP_PE_BWD(3, 24); }
+        else { if (E == 96) TULIP_PE_BWD(6, 32); else TULIP_PE_BWD(3, 32); }
 #undef TULIP_PE_BWD
         TULIP_CHECK_LAUNCH();
         return TULIP_OK;

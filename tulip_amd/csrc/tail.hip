@@ -60,57 +60,75 @@ __device__ __forceinline__ void expand_channel(const bf16_t* __restrict__ We, co
 // LeakyReLU(0.01)(z) = max(z, 0.01 z): the same value as the compare / select form, two instructions instead of three
 __device__ __forceinline__ float leaky01(float z) { return fmaxf(z, 0.01f * z); }
 
-__device__ __forceinline__ size_t pred_off(const TailGeom& g, int tok, int i) {
+// pred is (B, NCH, 4H, 4W): the offset of sub-row i of token tok in output channel k
+template <int NCH = 1>
+__device__ __forceinline__ size_t pred_off(const TailGeom& g, int tok, int i, int k = 0) {
     const int t = fast_div(tok, g.W), w = tok - t * g.W;
     const int b = fast_div(t, g.H), h = t - b * g.H;
-    return ((size_t)b * 4 * g.H + 4 * h + i) * (4 * g.W) + 4 * w;
+    return ((size_t)(b * NCH + k) * 4 * g.H + 4 * h + i) * (4 * g.W) + 4 * w;
+}
+
+// f(id) for id = 0 .. N - 1 over a 256-thread workgroup: one guarded pass for N <= 256
+template <int N, class F>
+__device__ __forceinline__ void for_ids256(F&& f) {
+    if constexpr (N <= 256) { if (threadIdx.x < N) f((int)threadIdx.x); }
+    else { for (int id = threadIdx.x; id < N; id += 256) f(id); }
 }
 
 // Work split: a workgroup owns 32 tokens; its 4 waves share them and each walks a quarter of the E channels
 // (the first version gave each wave 32 tokens and all E channels: 1 wave per SIMD and a 96-deep chain of
 // dependent L2 loads -- latency-bound at 85 / 111 us).  Forward: the four partial pixel sums meet in LDS.
-template <int KS>
+// NCH output channels (decoder_pred E -> NCH, wd = [NCH][E]): each lane keeps NCH pixel sums, the LDS reduction holds NCH planes
+template <int KS, int NCH>
 __global__ __launch_bounds__(256, 2) void tail_fwd_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                        const float* __restrict__ be, const float* __restrict__ wd,
                                                        float* __restrict__ pred, TailGeom g) {
-    __shared__ __attribute__((aligned(16))) float red[4][32][16];
+    __shared__ __attribute__((aligned(16))) float red[NCH][4][32][16];
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
     const int m0 = blockIdx.x * 32;
     bf16x8 xb[2][KS];
     load_x<KS>(xn, g, m0, li, gq, xb);
-    float pacc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float pacc[NCH][2][4] = {};
     const int cper = (g.E + 3) / 4, c0 = wid * cper, c1 = min(g.E, c0 + cper);
     auto channels = [&](auto F) {
         for (int c = c0; c < c1; ++c) {
             f32x4 acc[2];
             expand_channel<KS, decltype(F)::value>(We, g, c, li, gq, xb, acc);
             const float4 b4 = *(const float4*)(be + c * 16 + gq * 4);
-            const float wc = wd[c];
+            float wc[NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) wc[k] = wd[k * g.E + c];
             const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pacc[mf][r] += wc * leaky01(acc[mf][r] + bb[r]);
+                for (int r = 0; r < 4; ++r) {
+                    const float lz = leaky01(acc[mf][r] + bb[r]);
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) pacc[k][mf][r] += wc[k] * lz;
+                }
         }
     };
     if (g.E == KS * 32) channels(std::true_type{}); else channels(std::false_type{});      // (uniform)
 #pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
-        *(float4*)&red[wid][mf * 16 + li][gq * 4] = make_float4(pacc[mf][0], pacc[mf][1], pacc[mf][2], pacc[mf][3]);
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf)
+            *(float4*)&red[k][wid][mf * 16 + li][gq * 4] = make_float4(pacc[k][mf][0], pacc[k][mf][1], pacc[k][mf][2], pacc[k][mf][3]);
     __syncthreads();
-    if (threadIdx.x < 128) {
-        const int t = threadIdx.x >> 2, i = threadIdx.x & 3;   // token, sub-row i (4 pixels j = 0..3)
+    for_ids256<128 * NCH>([&](int id) {
+        const int k = NCH == 1 ? 0 : id >> 7, t = (NCH == 1 ? id : id & 127) >> 2, i = id & 3;   // channel, token, sub-row i (pixels j = 0..3)
         const int tok = m0 + t;
         if (tok < g.M) {
-            float4 o = *(const float4*)&red[0][t][i * 4];
+            float4 o = *(const float4*)&red[k][0][t][i * 4];
 #pragma unroll
             for (int w = 1; w < 4; ++w) {
-                const float4 v = *(const float4*)&red[w][t][i * 4];
+                const float4 v = *(const float4*)&red[k][w][t][i * 4];
                 o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
             }
-            *(float4*)(pred + pred_off(g, tok, i)) = o;
+            *(float4*)(pred + pred_off<NCH>(g, tok, i, k)) = o;
         }
-    }
+    });
 }
 
 // The same forward with norm_up (tulip.py:720) in front and the L1 / pixel loss partial sums (tulip.py:690-700) behind it, one
@@ -119,12 +137,13 @@ __global__ __launch_bounds__(256, 2) void tail_fwd_kernel(const bf16_t* __restri
 // leaves registers on the way to the expand conv); wave 0 also stores it (bf16) with the row statistics for the backward.
 struct TailNorm { const float* x; const float* gamma; const float* beta; float eps; bf16_t* xn; float* mean; float* rstd; };
 struct TailLoss { const float* target; float* partials; int log_transform; };
-template <int KS>
+template <int KS, int NCH>
 __global__ __launch_bounds__(256, 2) void tail_fwd_ln_kernel(const TailNorm nrm, const bf16_t* __restrict__ We,
                                                           const float* __restrict__ be, const float* __restrict__ wd,
                                                           float* __restrict__ pred, TailGeom g, const TailLoss ls) {
-    __shared__ __attribute__((aligned(16))) float red[4][32][16];
-    __shared__ float lred[2][2];
+    constexpr int LW = NCH == 1 ? 2 : 4;                                  // waves that hold pixels in the epilogue
+    __shared__ __attribute__((aligned(16))) float red[NCH][4][32][16];
+    __shared__ float lred[2][LW];
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
     const int m0 = blockIdx.x * 32;
     bf16x8 xb[2][KS];
@@ -177,60 +196,95 @@ __global__ __launch_bounds__(256, 2) void tail_fwd_ln_kernel(const TailNorm nrm,
             xb[mf][ks] = o;
         }
     }
-    float pacc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float pacc[NCH][2][4] = {};
     const int cper = (g.E + 3) / 4, c0 = wid * cper, c1 = min(g.E, c0 + cper);
     auto channels = [&](auto F) {
         for (int c = c0; c < c1; ++c) {
             f32x4 acc[2];
             expand_channel<KS, decltype(F)::value>(We, g, c, li, gq, xb, acc);
             const float4 b4 = *(const float4*)(be + c * 16 + gq * 4);
-            const float wc = wd[c];
+            float wc[NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) wc[k] = wd[k * g.E + c];
             const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pacc[mf][r] += wc * leaky01(acc[mf][r] + bb[r]);
+                for (int r = 0; r < 4; ++r) {
+                    const float lz = leaky01(acc[mf][r] + bb[r]);
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) pacc[k][mf][r] += wc[k] * lz;
+                }
         }
     };
     if (g.E == KS * 32) channels(std::true_type{}); else channels(std::false_type{});      // (uniform)
 #pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
-        *(float4*)&red[wid][mf * 16 + li][gq * 4] = make_float4(pacc[mf][0], pacc[mf][1], pacc[mf][2], pacc[mf][3]);
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf)
+            *(float4*)&red[k][wid][mf * 16 + li][gq * 4] = make_float4(pacc[k][mf][0], pacc[k][mf][1], pacc[k][mf][2], pacc[k][mf][3]);
     __syncthreads();
     float l0 = 0.f, l1 = 0.f;
-    if (threadIdx.x < 128) {
-        const int t = threadIdx.x >> 2, i = threadIdx.x & 3;   // token, sub-row i (4 pixels j = 0..3)
-        const int tok = m0 + t;
-        if (tok < g.M) {
-            float4 o = *(const float4*)&red[0][t][i * 4];
+    if constexpr (NCH == 1) {
+        if (threadIdx.x < 128) {
+            const int t = threadIdx.x >> 2, i = threadIdx.x & 3;   // token, sub-row i (4 pixels j = 0..3)
+            const int tok = m0 + t;
+            if (tok < g.M) {
+                float4 o = *(const float4*)&red[0][0][t][i * 4];
 #pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const float4 v = *(const float4*)&red[w][t][i * 4];
-                o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                for (int w = 1; w < 4; ++w) {
+                    const float4 v = *(const float4*)&red[0][w][t][i * 4];
+                    o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                }
+                const size_t po = pred_off(g, tok, i);
+                *(float4*)(pred + po) = o;
+                if (ls.partials) {
+                    const float4 q = *(const float4*)(ls.target + po);
+                    l0 = (fabsf(o.x - q.x) + fabsf(o.y - q.y)) + (fabsf(o.z - q.z) + fabsf(o.w - q.w));
+                    if (ls.log_transform)
+                        l1 = (fabsf(expm1f(o.x) - expm1f(q.x)) + fabsf(expm1f(o.y) - expm1f(q.y))) +
+                             (fabsf(expm1f(o.z) - expm1f(q.z)) + fabsf(expm1f(o.w) - expm1f(q.w)));
+                }
             }
-            const size_t po = pred_off(g, tok, i);
-            *(float4*)(pred + po) = o;
-            if (ls.partials) {
-                const float4 q = *(const float4*)(ls.target + po);
-                l0 = (fabsf(o.x - q.x) + fabsf(o.y - q.y)) + (fabsf(o.z - q.z) + fabsf(o.w - q.w));
-                if (ls.log_transform)
-                    l1 = (fabsf(expm1f(o.x) - expm1f(q.x)) + fabsf(expm1f(o.y) - expm1f(q.y))) +
-                         (fabsf(expm1f(o.z) - expm1f(q.z)) + fabsf(expm1f(o.w) - expm1f(q.w)));
+        }
+    } else {
+        for (int id = threadIdx.x; id < 128 * NCH; id += 256) {
+            const int k = id >> 7, t = (id & 127) >> 2, i = id & 3;   // channel, token, sub-row i
+            const int tok = m0 + t;
+            if (tok < g.M) {
+                float4 o = *(const float4*)&red[k][0][t][i * 4];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const float4 v = *(const float4*)&red[k][w][t][i * 4];
+                    o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                }
+                const size_t po = pred_off<NCH>(g, tok, i, k);
+                *(float4*)(pred + po) = o;
+                if (ls.partials) {
+                    const float4 q = *(const float4*)(ls.target + po);
+                    l0 += (fabsf(o.x - q.x) + fabsf(o.y - q.y)) + (fabsf(o.z - q.z) + fabsf(o.w - q.w));
+                    if (ls.log_transform)
+                        l1 += (fabsf(expm1f(o.x) - expm1f(q.x)) + fabsf(expm1f(o.y) - expm1f(q.y))) +
+                              (fabsf(expm1f(o.z) - expm1f(q.z)) + fabsf(expm1f(o.w) - expm1f(q.w)));
+                }
             }
         }
     }
     if (ls.partials) {                                          // uniform
         l0 = group_sum<64>(l0); l1 = group_sum<64>(l1);
-        if (lane == 0 && wid < 2) { lred[0][wid] = l0; lred[1][wid] = l1; }
+        if (lane == 0 && wid < LW) { lred[0][wid] = l0; lred[1][wid] = l1; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            ls.partials[blockIdx.x * 2] = lred[0][0] + lred[0][1];
-            ls.partials[blockIdx.x * 2 + 1] = lred[1][0] + lred[1][1];
+            float s0 = lred[0][0], s1 = lred[1][0];
+#pragma unroll
+            for (int w = 1; w < LW; ++w) { s0 += lred[0][w]; s1 += lred[1][w]; }
+            ls.partials[blockIdx.x * 2] = s0;
+            ls.partials[blockIdx.x * 2 + 1] = s1;
         }
     }
 }
 
-template <int KS>
+template <int KS, int NCH>
 __global__ __launch_bounds__(256, 2) void tail_bwd_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                        const float* __restrict__ be, const float* __restrict__ wd,
                                                        const float* __restrict__ dpred, bf16_t* __restrict__ dz,
@@ -238,31 +292,34 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_kernel(const bf16_t* __restri
                                                        const float* __restrict__ gscale_dev, float gscale) {
     // target != NULL: `dpred` is the forward's pred and the L1 gradient sign(pred-target)*g/N
     // (tulip.py:692-693 backward) is formed here instead of by a separate pass.
-    __shared__ float lds_dwd[128];
+    // NCH > 1: the upstream value of expand channel c is sum_k wd[k][c] dpred_k; dwd rows are [NCH][128]
+    __shared__ float lds_dwd[NCH * 128];
     __shared__ __attribute__((aligned(16))) bf16_t stile[4][32 * 72];   // 64 cols + 8 pad (bank spread)
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
-    if (threadIdx.x < 128) lds_dwd[threadIdx.x] = 0.f;
+    for_ids256<NCH * 128>([&](int id) { lds_dwd[id] = 0.f; });
     __syncthreads();
     const int m0 = blockIdx.x * 32;
     bf16x8 xb[2][KS];
     load_x<KS>(xn, g, m0, li, gq, xb);
-    float dp[2][4];
+    float dp[NCH][2][4];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
 #pragma unroll
     for (int mf = 0; mf < 2; ++mf) {
         const int tok = m0 + mf * 16 + li;
         float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
         if (tok < g.M) {
-            const size_t po = pred_off(g, tok, gq);
+            const size_t po = pred_off<NCH>(g, tok, gq, k);
             d = *(const float4*)(dpred + po);
             if (target) {
                 const float4 t = *(const float4*)(target + po);
-                const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)g.M);
+                const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)(NCH * g.M));
                 const float e[4] = {d.x - t.x, d.y - t.y, d.z - t.z, d.w - t.w};
                 d = make_float4(e[0] > 0.f ? gs : (e[0] < 0.f ? -gs : 0.f), e[1] > 0.f ? gs : (e[1] < 0.f ? -gs : 0.f),
                                 e[2] > 0.f ? gs : (e[2] < 0.f ? -gs : 0.f), e[3] > 0.f ? gs : (e[3] < 0.f ? -gs : 0.f));
             }
         }
-        dp[mf][0] = d.x; dp[mf][1] = d.y; dp[mf][2] = d.z; dp[mf][3] = d.w;
+        dp[k][mf][0] = d.x; dp[k][mf][1] = d.y; dp[k][mf][2] = d.z; dp[k][mf][3] = d.w;
     }
     const int N = 16 * g.E;
     const int cper = (g.E + 3) / 4, c0 = wid * cper, c1 = min(g.E, c0 + cper);
@@ -277,9 +334,11 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_kernel(const bf16_t* __restri
             f32x4 acc[2];
             expand_channel<KS>(We, g, c, li, gq, xb, acc);
             const float4 b4 = *(const float4*)(be + c * 16 + gq * 4);
-            const float wc = wd[c];
+            float wc[NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) wc[k] = wd[k * g.E + c];
             const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-            float part = 0.f;
+            float part[NCH] = {};
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf) {
                 float o[4];
@@ -287,14 +346,22 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_kernel(const bf16_t* __restri
                 for (int r = 0; r < 4; ++r) {
                     const float z = acc[mf][r] + bb[r];
                     const bool pos = z > 0.f;
-                    part += dp[mf][r] * (pos ? z : 0.01f * z);
-                    o[r] = dp[mf][r] * wc * (pos ? 1.0f : 0.01f);
+                    float u = dp[0][mf][r] * wc[0];
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        part[k] += dp[k][mf][r] * (pos ? z : 0.01f * z);
+                        if (k > 0) u += dp[k][mf][r] * wc[k];
+                    }
+                    o[r] = u * (pos ? 1.0f : 0.01f);
                 }
                 *(uint2*)(tile + (mf * 16 + li) * 72 + cc * 16 + gq * 4) =
                     make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
             }
-            part = group_sum<64>(part);
-            if (lane == 0) lds_dwd[c] = part;          // channel c belongs to this wave alone
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                part[k] = group_sum<64>(part[k]);
+                if (lane == 0) lds_dwd[k * 128 + c] = part[k];   // channel c belongs to this wave alone
+            }
         }
         // wave-private tile: LDS ops of one wave execute in order, no barrier needed
         const int chunks = ng * 2;                      // 16-B chunks per token row
@@ -306,8 +373,12 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_kernel(const bf16_t* __restri
         }
     }
     __syncthreads();
-    // one plain partial row per workgroup: dwd[blockIdx.x][128] (folded by tulip_reduce_rows2)
-    if (threadIdx.x < 128) dwd[(size_t)blockIdx.x * 128 + threadIdx.x] = threadIdx.x < g.E ? lds_dwd[threadIdx.x] : 0.f;
+    // one plain partial row per workgroup: dwd[blockIdx.x][NCH][128] (folded by tulip_reduce_rows2)
+    if constexpr (NCH == 1) {
+        if (threadIdx.x < 128) dwd[(size_t)blockIdx.x * 128 + threadIdx.x] = threadIdx.x < g.E ? lds_dwd[threadIdx.x] : 0.f;
+    } else {
+        for (int id = threadIdx.x; id < NCH * 128; id += 256) dwd[(size_t)blockIdx.x * (NCH * 128) + id] = (id & 127) < g.E ? lds_dwd[id] : 0.f;
+    }
 }
 
 
@@ -360,7 +431,7 @@ struct TailNormBwd {
     const float* x; const float* mean; const float* rstd; const float* gamma;
     float* dx; bf16_t* dx_bf16; const float* cast_rowscale; int cast_rows_per_sample; float* param_partials;
 };
-template <int KS, int NB>
+template <int KS, int NB, int NCH>
 __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                              const float* __restrict__ be, const float* __restrict__ wd,
                                                              const float* __restrict__ dpred, bf16_t* __restrict__ dxn,
@@ -370,26 +441,41 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
     constexpr int E = NB * 16, PITCH = tr_pitch(E), RP = E + 4;        // RP: fp32 row pitch of the cross-wave reduction
     constexpr int TILE = 32 * PITCH, RED = 32 * RP * 4;
     constexpr int MAIN = 4 * (TILE > RED ? TILE : RED);
-    __shared__ float lds_dwd[128];
+    __shared__ float lds_dwd[NCH * 128];
     // phase 1: four wave-private [32 output channels][E] tiles of We; phase 2 (overlaid): four [32 tokens][E] fp32 partial dxn;
     // behind them the [32 tokens][2E] LayerNorm affine-gradient terms of the fused norm_up backward
     __shared__ __attribute__((aligned(16))) unsigned char smem[MAIN + 32 * 2 * E * 4];
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
-    if (threadIdx.x < 128) lds_dwd[threadIdx.x] = 0.f;
+    if constexpr (NCH == 1) { if (threadIdx.x < 128) lds_dwd[threadIdx.x] = 0.f; }
+    else { for (int id = threadIdx.x; id < NCH * 128; id += 256) lds_dwd[id] = 0.f; }
     __syncthreads();
     const int m0 = blockIdx.x * 32;
     bf16x8 xb[2][KS];
     load_x<KS>(xn, g, m0, li, gq, xb);
-    float dp[2][4], dq[2][4];
-    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)g.M);
+    // NCH == 1: dp / dq = leaky_grad_sel's pair of the one upstream value; NCH > 1: dpk = the NCH upstream values, mixed per
+    // expand channel c into sum_k wd[k][c] dpk[k] below
+    float dp[2][4], dq[2][4], dpk[NCH][2][4];
+    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)(NCH * g.M));
+    if constexpr (NCH == 1) {
 #pragma unroll
-    for (int mf = 0; mf < 2; ++mf) {
-        const int tok = m0 + mf * 16 + li;
-        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tok < g.M) d = pred_grad4(dpred, target, pred_off(g, tok, gq), gs);
-        dp[mf][0] = d.x; dp[mf][1] = d.y; dp[mf][2] = d.z; dp[mf][3] = d.w;
+        for (int mf = 0; mf < 2; ++mf) {
+            const int tok = m0 + mf * 16 + li;
+            float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tok < g.M) d = pred_grad4(dpred, target, pred_off(g, tok, gq), gs);
+            dp[mf][0] = d.x; dp[mf][1] = d.y; dp[mf][2] = d.z; dp[mf][3] = d.w;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { dq[mf][r] = 0.495f * dp[mf][r]; dp[mf][r] *= 0.505f; }     // leaky_grad_sel's pair
+            for (int r = 0; r < 4; ++r) { dq[mf][r] = 0.495f * dp[mf][r]; dp[mf][r] *= 0.505f; }     // leaky_grad_sel's pair
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int mf = 0; mf < 2; ++mf) {
+                const int tok = m0 + mf * 16 + li;
+                float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (tok < g.M) d = pred_grad4(dpred, target, pred_off<NCH>(g, tok, gq, k), gs);
+                dpk[k][mf][0] = d.x; dpk[k][mf][1] = d.y; dpk[k][mf][2] = d.z; dpk[k][mf][3] = d.w;
+            }
     }
     const int cper = g.E / 4, c0 = wid * cper, c1 = c0 + cper;          // E % 16 == 0: an even number of channels per wave
     unsigned char* tile = smem + wid * TILE;
@@ -414,8 +500,10 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
                 wa[ks] = v;
             }
             const float4 b4 = *(const float4*)(be + (c + cc) * 16 + gq * 4);
-            const float wc = wd[c + cc];
-            float part = 0.f;
+            float wc[NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) wc[k] = wd[k * E + c + cc];
+            float part[NCH] = {};
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf) {
                 f32x4 a = {b4.x, b4.y, b4.z, b4.w};                       // the MFMAs accumulate on top of the bias
@@ -425,14 +513,32 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
                 float o[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float sel = leaky_grad_sel(a[r], dp[mf][r], dq[mf][r]);
-                    part = fmaf(sel, a[r], part);                         // d(decoder_pred.weight[c]) += dpred * leaky(z)
-                    o[r] = sel * wc;
+                    if constexpr (NCH == 1) {
+                        const float sel = leaky_grad_sel(a[r], dp[mf][r], dq[mf][r]);
+                        part[0] = fmaf(sel, a[r], part[0]);               // d(decoder_pred.weight[c]) += dpred * leaky(z)
+                        o[r] = sel * wc[0];
+                    } else {
+                        float u = wc[0] * dpk[0][mf][r];                  // sum_k wd[k][c] dpred_k
+#pragma unroll
+                        for (int k = 1; k < NCH; ++k) u = fmaf(wc[k], dpk[k][mf][r], u);
+                        const float lz = leaky01(a[r]);
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) part[k] = fmaf(dpk[k][mf][r], lz, part[k]);   // d(decoder_pred.weight[k][c])
+                        o[r] = leaky_grad_sel(a[r], 0.505f * u, 0.495f * u);
+                    }
                 }
                 ob[cc][mf] = pack4_t(o[0], o[1], o[2], o[3]);            // dz[token li][(c+cc)*16 + 4gq + r], bf16
             }
-            part = group_sum<64>(part);
-            if (lane == 0) lds_dwd[c + cc] = part;                        // channel c belongs to this wave alone
+            if constexpr (NCH == 1) {
+                const float pt = group_sum<64>(part[0]);
+                if (lane == 0) lds_dwd[c + cc] = pt;                      // channel c belongs to this wave alone
+            } else {
+#pragma unroll
+                for (int k = 0; k < NCH; ++k) {
+                    part[k] = group_sum<64>(part[k]);
+                    if (lane == 0) lds_dwd[k * 128 + c + cc] = part[k];
+                }
+            }
         }
         // dxn^T[k][token] += We^T[k][oc] . dz[oc][token] over the pair's 32 output channels (k order: 4gq.., 16+4gq..)
         const bf16x8 dzf[2] = {mfma_operand_fence(cat8_t(ob[0][0], ob[1][0])), mfma_operand_fence(cat8_t(ob[0][1], ob[1][1]))};
@@ -524,7 +630,11 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
             }
         }
     }
-    if (threadIdx.x < 128) dwd[(size_t)blockIdx.x * 128 + threadIdx.x] = threadIdx.x < g.E ? lds_dwd[threadIdx.x] : 0.f;
+    if constexpr (NCH == 1) {
+        if (threadIdx.x < 128) dwd[(size_t)blockIdx.x * 128 + threadIdx.x] = threadIdx.x < g.E ? lds_dwd[threadIdx.x] : 0.f;
+    } else {
+        for (int id = threadIdx.x; id < NCH * 128; id += 256) dwd[(size_t)blockIdx.x * (NCH * 128) + id] = (id & 127) < g.E ? lds_dwd[id] : 0.f;
+    }
 }
 
 template <int N, class F>
@@ -535,26 +645,29 @@ __device__ __forceinline__ void static_for_t(F&& f) {
 // one workgroup: NWV waves x NC channels (a slice of 16 NWV NC output channels of the expand conv) over `steps` 32-token
 // steps.  Every slice re-reads xn and pred / target (320 B per token: more than a 12th of the dz row it replaces), so the
 // slices are made as wide as the accumulators allow: 8 waves x 3 channels = 4 slices at E = 96.
-template <int KS, int NB, int NC, int NWV>
+//
+// NCH > 1: dz of expand channel c is leaky'(z) sum_k wd[k][c] dpred_k, a different mix per channel, so the mix is formed in front
+// of the MFMAs (it cannot be factored out as the single decoder_pred weight is at NCH == 1) and pred / target hold NCH planes
+template <int KS, int NB, int NC, int NWV, int NCH>
 __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_wgrad_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                       const float* __restrict__ be, const float* __restrict__ wd,
                                                       const float* __restrict__ dpred, const float* __restrict__ target,
                                                       const float* __restrict__ gscale_dev, float gscale,
                                                       float* __restrict__ slab_w, float* __restrict__ slab_b, TailGeom g,
                                                       int nslices, int steps_per_split, int wshift) {
-    constexpr int NT = 64 * NWV;
+    constexpr int NT = 64 * NWV, PD = (128 * NCH + NT - 1) / NT;        // PD: pred pieces per thread (one channel plane each)
     constexpr int E = NB * 16, PITCH = tr_pitch(E), CPR = E / 8, NCHUNK = 32 * CPR, PER = (NCHUNK + NT - 1) / NT;
     __shared__ __attribute__((aligned(16))) unsigned char xt[2][32 * PITCH];
-    __shared__ __attribute__((aligned(16))) float dpt[2][16][36];          // [sub-pixel][token], rows padded to 144 B
+    __shared__ __attribute__((aligned(16))) float dpt[2][NCH][16][36];     // [channel][sub-pixel][token], rows padded to 144 B
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
     const int slice = blockIdx.x % nslices, split = blockIdx.x / nslices;
     const int cb = (slice * NWV + wid) * NC;                               // nslices = E / (NWV NC)
     const int total = (g.M + 31) >> 5;
     const int s0 = split * steps_per_split, s1 = min(total, s0 + steps_per_split);
-    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)g.M);
+    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)(NCH * g.M));
     // this wave's rows of We as B operands (column = output channel li of channel cb + cc), its bias and decoder weights
     bf16x8 wb[NC][KS];
-    float bev[NC], wdv[NC];
+    float bev[NC], wdv[NCH][NC];
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) {
 #pragma unroll
@@ -565,7 +678,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
             wb[cc][ks] = v;
         }
         bev[cc] = be[(cb + cc) * 16 + li];
-        wdv[cc] = wd[cb + cc];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) wdv[k][cc] = wd[k * E + cb + cc];
     }
     f32x4 acc[NC][NB];
     float bsum[NC];
@@ -582,7 +696,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
     constexpr int RING = NWV == 8 ? 2 : 3;                                   // (256 registers per wave with 8 waves)
     typedef unsigned u32x4_s __attribute__((ext_vector_type(4)));
     u32x4_s xr[RING][PER];
-    float4 dr[RING], tr[RING];
+    float4 dr[RING][PD], tr[RING][PD];
     const float* tsrc = target ? target : dpred;
     const int pt = (threadIdx.x & 127) >> 2, pi = threadIdx.x & 3;          // (token, sub-row) of this thread's pred piece
     // Address arithmetic is the vector-ALU budget of this kernel (a 64-bit multiply-add chain per load and step was more
@@ -610,11 +724,21 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
             if (!full) off = (unsigned)min(xrow[i], g.M - 1 - m0) * (E * 2) + xcol[i];
             xr[r][i] = *(const u32x4_s*)(xb + off);
         }
-        unsigned po;
-        if (wshift >= 0 && full) po = (unsigned)(16 * (m0 >> wshift) * g.W + 4 * (m0 & (g.W - 1))) + ppix;
-        else po = (unsigned)pred_off(g, min(m0 + pt, g.M - 1), pi);
-        dr[r] = *(const float4*)(dpred + po);
-        tr[r] = *(const float4*)(tsrc + po);
+        if constexpr (NCH == 1) {
+            unsigned po;
+            if (wshift >= 0 && full) po = (unsigned)(16 * (m0 >> wshift) * g.W + 4 * (m0 & (g.W - 1))) + ppix;
+            else po = (unsigned)pred_off(g, min(m0 + pt, g.M - 1), pi);
+            dr[r][0] = *(const float4*)(dpred + po);
+            tr[r][0] = *(const float4*)(tsrc + po);
+        } else {
+#pragma unroll
+            for (int j = 0; j < PD; ++j) {                                     // plane k = id >> 7 (clamped: loads are unconditional)
+                const int kp = min((int)(threadIdx.x >> 7) + j * (NT / 128), NCH - 1);
+                const unsigned po = (unsigned)pred_off<NCH>(g, min(m0 + pt, g.M - 1), pi, kp);
+                dr[r][j] = *(const float4*)(dpred + po);
+                tr[r][j] = *(const float4*)(tsrc + po);
+            }
+        }
     };
     auto stash = [&](auto R, int buf, int step) {
         constexpr int r = decltype(R)::value;
@@ -629,16 +753,35 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
                 *(u32x4_s*)(xt[buf] + t * PITCH + k8 * 16) = v;
             }
         }
-        if (threadIdx.x < 128) {
-            float4 d = dr[r];
-            if (target) {
-                const float4 q = tr[r];
-                const float e[4] = {d.x - q.x, d.y - q.y, d.z - q.z, d.w - q.w};
-                d = make_float4(e[0] > 0.f ? gs : (e[0] < 0.f ? -gs : 0.f), e[1] > 0.f ? gs : (e[1] < 0.f ? -gs : 0.f),
-                                e[2] > 0.f ? gs : (e[2] < 0.f ? -gs : 0.f), e[3] > 0.f ? gs : (e[3] < 0.f ? -gs : 0.f));
+        if constexpr (NCH == 1) {
+            if (threadIdx.x < 128) {
+                float4 d = dr[r][0];
+                if (target) {
+                    const float4 q = tr[r][0];
+                    const float e[4] = {d.x - q.x, d.y - q.y, d.z - q.z, d.w - q.w};
+                    d = make_float4(e[0] > 0.f ? gs : (e[0] < 0.f ? -gs : 0.f), e[1] > 0.f ? gs : (e[1] < 0.f ? -gs : 0.f),
+                                    e[2] > 0.f ? gs : (e[2] < 0.f ? -gs : 0.f), e[3] > 0.f ? gs : (e[3] < 0.f ? -gs : 0.f));
+                }
+                if (m0 + pt >= g.M) d = make_float4(0.f, 0.f, 0.f, 0.f);
+                dpt[buf][0][pi * 4][pt] = d.x; dpt[buf][0][pi * 4 + 1][pt] = d.y; dpt[buf][0][pi * 4 + 2][pt] = d.z; dpt[buf][0][pi * 4 + 3][pt] = d.w;
             }
-            if (m0 + pt >= g.M) d = make_float4(0.f, 0.f, 0.f, 0.f);
-            dpt[buf][pi * 4][pt] = d.x; dpt[buf][pi * 4 + 1][pt] = d.y; dpt[buf][pi * 4 + 2][pt] = d.z; dpt[buf][pi * 4 + 3][pt] = d.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < PD; ++j) {
+                const int id = threadIdx.x + j * NT;
+                if (id < 128 * NCH) {
+                    float4 d = dr[r][j];
+                    if (target) {
+                        const float4 q = tr[r][j];
+                        const float e[4] = {d.x - q.x, d.y - q.y, d.z - q.z, d.w - q.w};
+                        d = make_float4(e[0] > 0.f ? gs : (e[0] < 0.f ? -gs : 0.f), e[1] > 0.f ? gs : (e[1] < 0.f ? -gs : 0.f),
+                                        e[2] > 0.f ? gs : (e[2] < 0.f ? -gs : 0.f), e[3] > 0.f ? gs : (e[3] < 0.f ? -gs : 0.f));
+                    }
+                    if (m0 + pt >= g.M) d = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float (*dk)[36] = dpt[buf][id >> 7];
+                    dk[pi * 4][pt] = d.x; dk[pi * 4 + 1][pt] = d.y; dk[pi * 4 + 2][pt] = d.z; dk[pi * 4 + 3][pt] = d.w;
+                }
+            }
         }
     };
     auto compute = [&](int buf) {
@@ -657,13 +800,24 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
 #pragma unroll
             for (int n = 0; n < NB; ++n) xT[n] = cat8_t(trr_t(trp + 32 * n), trr_t(trp + 32 * n + 16 * PITCH));   // row = channel 16n + li
             // the upstream gradient of this lane's sub-pixel li at its 2 x 4 tokens, as the pair leaky_grad_sel takes
-            float dpl[2][4], dql[2][4];
+            // (NCH > 1: the raw values of every plane, mixed per channel below)
+            float dpl[2][4], dql[2][4], dk[NCH][2][4];
+            if constexpr (NCH == 1) {
 #pragma unroll
-            for (int mf = 0; mf < 2; ++mf) {
-                const float4 d = *(const float4*)&dpt[buf][li][mf * 16 + 4 * gq];
-                dpl[mf][0] = d.x; dpl[mf][1] = d.y; dpl[mf][2] = d.z; dpl[mf][3] = d.w;
+                for (int mf = 0; mf < 2; ++mf) {
+                    const float4 d = *(const float4*)&dpt[buf][0][li][mf * 16 + 4 * gq];
+                    dpl[mf][0] = d.x; dpl[mf][1] = d.y; dpl[mf][2] = d.z; dpl[mf][3] = d.w;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { dql[mf][r] = 0.495f * dpl[mf][r]; dpl[mf][r] *= 0.505f; }   // leaky_grad_sel's pair
+                    for (int r = 0; r < 4; ++r) { dql[mf][r] = 0.495f * dpl[mf][r]; dpl[mf][r] *= 0.505f; }   // leaky_grad_sel's pair
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NCH; ++k)
+#pragma unroll
+                    for (int mf = 0; mf < 2; ++mf) {
+                        const float4 d = *(const float4*)&dpt[buf][k][li][mf * 16 + 4 * gq];
+                        dk[k][mf][0] = d.x; dk[k][mf][1] = d.y; dk[k][mf][2] = d.z; dk[k][mf][3] = d.w;
+                    }
             }
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) {
@@ -673,11 +827,21 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
                     f32x4 z = {bev[cc], bev[cc], bev[cc], bev[cc]};              // z[r] = Z[token mf*16 + 4gq + r][channel li], on top of the bias
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[mf][ks], wb[cc][ks], z, 0, 0, 0);
-                    // dz / decoder_pred.weight[c]: the per-channel factor multiplies the accumulators once, at the end (the
-                    // kernel is vector-ALU bound: 3 instructions per element here)
+                    // NCH == 1: dz / decoder_pred.weight[c]: the per-channel factor multiplies the accumulators once, at the end
+                    // (the kernel is vector-ALU bound: 3 instructions per element here).  NCH > 1: the mixed upstream value
                     float o[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { o[r] = leaky_grad_sel(z[r], dpl[mf][r], dql[mf][r]); bsum[cc] += o[r]; }
+                    for (int r = 0; r < 4; ++r) {
+                        if constexpr (NCH == 1) {
+                            o[r] = leaky_grad_sel(z[r], dpl[mf][r], dql[mf][r]);
+                        } else {
+                            float u = wdv[0][cc] * dk[0][mf][r];
+#pragma unroll
+                            for (int k = 1; k < NCH; ++k) u = fmaf(wdv[k][cc], dk[k][mf][r], u);
+                            o[r] = leaky_grad_sel(z[r], 0.505f * u, 0.495f * u);
+                        }
+                        bsum[cc] += o[r];
+                    }
                     ob[mf] = pack4_t(o[0], o[1], o[2], o[3]);
                 }
                 const bf16x8 dzf = mfma_operand_fence(cat8_t(ob[0], ob[1]));    // contraction = tokens 4gq.., 16+4gq..
@@ -707,7 +871,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) {
         const int oc = (cb + cc) * 16 + li;
-        const float wc = wdv[cc];
+        const float wc = NCH == 1 ? wdv[0][cc] : 1.0f;                   // (NCH > 1: mixed in front of the MFMAs)
 #pragma unroll
         for (int n = 0; n < NB; ++n)
             *(float4*)(ow + (size_t)oc * E + 16 * n + 4 * gq) =
@@ -720,16 +884,48 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
 
 }  // namespace
 
-extern "C" int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
-                              int B, int H, int W, int E, hipStream_t stream) {
-    if (E <= 0 || (E & 7) || E > 128) return TULIP_ERR_ARG;
+// in_chans: decoder_pred's output channels (NCH of the kernels), 1 .. 4
+#define TULIP_NCH_SWITCH(X) \
+    switch (in_chans) { case 1: X(1); break; case 2: X(2); break; case 3: X(3); break; default: X(4); break; }
+
+static bool bad_chans(int in_chans) { return in_chans < 1 || in_chans > 4; }
+
+extern "C" int tulip_tail_fwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                int B, int H, int W, int E, hipStream_t stream, int in_chans) {
+    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans)) return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     const dim3 grid((g.M + 31) / 32), block(256);
     const int ks = (E + 31) / 32;
-    if (ks <= 2) hipLaunchKernelGGL(tail_fwd_kernel<2>, grid, block, 0, stream, xn, We, be, wd, pred, g);
-    else if (ks == 3) hipLaunchKernelGGL(tail_fwd_kernel<3>, grid, block, 0, stream, xn, We, be, wd, pred, g);
-    else hipLaunchKernelGGL(tail_fwd_kernel<4>, grid, block, 0, stream, xn, We, be, wd, pred, g);
+#define TULIP_TF(NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((tail_fwd_kernel<2, NCH>), grid, block, 0, stream, xn, We, be, wd, pred, g); \
+    else if (ks == 3) hipLaunchKernelGGL((tail_fwd_kernel<3, NCH>), grid, block, 0, stream, xn, We, be, wd, pred, g); \
+    else hipLaunchKernelGGL((tail_fwd_kernel<4, NCH>), grid, block, 0, stream, xn, We, be, wd, pred, g);
+    TULIP_NCH_SWITCH(TULIP_TF)
+#undef TULIP_TF
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
+                              int B, int H, int W, int E, hipStream_t stream) {
+    return tulip_tail_fwd_c(xn, We, be, wd, pred, B, H, W, E, stream, 1);
+}
+
+extern "C" int tulip_tail_bwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                const float* dpred, uint16_t* dz, float* dwd, int B, int H, int W, int E,
+                                const float* target, const float* gscale_dev, float gscale, hipStream_t stream, int in_chans) {
+    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans)) return TULIP_ERR_ARG;
+    TailGeom g{B * H * W, H, W, E};
+    if (g.M <= 0) return TULIP_OK;
+    const dim3 grid((g.M + 31) / 32), block(256);
+    const int ks = (E + 31) / 32;
+#define TULIP_TB(NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((tail_bwd_kernel<2, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
+    else if (ks == 3) hipLaunchKernelGGL((tail_bwd_kernel<3, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
+    else hipLaunchKernelGGL((tail_bwd_kernel<4, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
+    TULIP_NCH_SWITCH(TULIP_TB)
+#undef TULIP_TB
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
@@ -737,51 +933,64 @@ extern "C" int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const floa
 extern "C" int tulip_tail_bwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                               const float* dpred, uint16_t* dz, float* dwd, int B, int H, int W, int E,
                               const float* target, const float* gscale_dev, float gscale, hipStream_t stream) {
-    if (E <= 0 || (E & 7) || E > 128) return TULIP_ERR_ARG;
-    TailGeom g{B * H * W, H, W, E};
-    if (g.M <= 0) return TULIP_OK;
-    const dim3 grid((g.M + 31) / 32), block(256);
-    const int ks = (E + 31) / 32;
-    if (ks <= 2) hipLaunchKernelGGL(tail_bwd_kernel<2>, grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
-    else if (ks == 3) hipLaunchKernelGGL(tail_bwd_kernel<3>, grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
-    else hipLaunchKernelGGL(tail_bwd_kernel<4>, grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return tulip_tail_bwd_c(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1);
 }
 
 extern "C" int tulip_tail_fused_bwd_supported(int E) { return E > 0 && E % 16 == 0 && E <= 128; }
 
 static int tail_bwd_dgrad_impl(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                                uint16_t* dxn, float* dwd, int B, int H, int W, int E, const float* target,
-                               const float* gscale_dev, float gscale, const TailNormBwd& nb, hipStream_t stream) {
-    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !dwd) return TULIP_ERR_ARG;
+                               const float* gscale_dev, float gscale, const TailNormBwd& nb, hipStream_t stream, int in_chans) {
+    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !dwd || bad_chans(in_chans)) return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     const dim3 grid((g.M + 31) / 32), block(256);
-#define TULIP_TBD(KS, NB) \
-    hipLaunchKernelGGL((tail_bwd_dgrad_kernel<KS, NB>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+#define TULIP_TBD(KS, NB, NCH) \
+    hipLaunchKernelGGL((tail_bwd_dgrad_kernel<KS, NB, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
                        (bf16_t*)dxn, dwd, g, target, gscale_dev, gscale, nb)
-    switch (E / 16) {
-        case 1: TULIP_TBD(1, 1); break;
-        case 2: TULIP_TBD(1, 2); break;
-        case 3: TULIP_TBD(2, 3); break;
-        case 4: TULIP_TBD(2, 4); break;
-        case 5: TULIP_TBD(3, 5); break;
-        case 6: TULIP_TBD(3, 6); break;
-        case 7: TULIP_TBD(4, 7); break;
-        default: TULIP_TBD(4, 8); break;
+#define TULIP_TBD_E(NCH) \
+    switch (E / 16) { \
+        case 1: TULIP_TBD(1, 1, NCH); break; \
+        case 2: TULIP_TBD(1, 2, NCH); break; \
+        case 3: TULIP_TBD(2, 3, NCH); break; \
+        case 4: TULIP_TBD(2, 4, NCH); break; \
+        case 5: TULIP_TBD(3, 5, NCH); break; \
+        case 6: TULIP_TBD(3, 6, NCH); break; \
+        case 7: TULIP_TBD(4, 7, NCH); break; \
+        default: TULIP_TBD(4, 8, NCH); break; \
     }
+    TULIP_NCH_SWITCH(TULIP_TBD_E)
+#undef TULIP_TBD_E
 #undef TULIP_TBD
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
 
+extern "C" int tulip_tail_bwd_dgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                      const float* dpred, uint16_t* dxn, float* dwd, int B, int H, int W, int E,
+                                      const float* target, const float* gscale_dev, float gscale, hipStream_t stream,
+                                      int in_chans) {
+    if (!dxn) return TULIP_ERR_ARG;
+    const TailNormBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr};
+    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, none, stream, in_chans);
+}
+
 extern "C" int tulip_tail_bwd_dgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                                     const float* dpred, uint16_t* dxn, float* dwd, int B, int H, int W, int E,
                                     const float* target, const float* gscale_dev, float gscale, hipStream_t stream) {
-    if (!dxn) return TULIP_ERR_ARG;
-    const TailNormBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr};
-    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, none, stream);
+    return tulip_tail_bwd_dgrad_c(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1);
+}
+
+extern "C" int tulip_tail_bwd_dgrad_ln_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                         const float* dpred, float* dwd, int B, int H, int W, int E, const float* target,
+                                         const float* gscale_dev, float gscale, const float* x, const float* mean,
+                                         const float* rstd, const float* gamma, float* dx, uint16_t* dx_bf16,
+                                         const float* cast_rowscale, int cast_rows_per_sample, float* ln_partials,
+                                         hipStream_t stream, int in_chans) {
+    if (!x || !mean || !rstd || !gamma || !dx) return TULIP_ERR_ARG;
+    const TailNormBwd nb{x, mean, rstd, gamma, dx, (bf16_t*)dx_bf16, cast_rowscale,
+                         cast_rows_per_sample > 0 ? cast_rows_per_sample : 1, ln_partials};
+    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, nullptr, dwd, B, H, W, E, target, gscale_dev, gscale, nb, stream, in_chans);
 }
 
 extern "C" int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
@@ -790,18 +999,16 @@ extern "C" int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, c
                                        const float* rstd, const float* gamma, float* dx, uint16_t* dx_bf16,
                                        const float* cast_rowscale, int cast_rows_per_sample, float* ln_partials,
                                        hipStream_t stream) {
-    if (!x || !mean || !rstd || !gamma || !dx) return TULIP_ERR_ARG;
-    const TailNormBwd nb{x, mean, rstd, gamma, dx, (bf16_t*)dx_bf16, cast_rowscale,
-                         cast_rows_per_sample > 0 ? cast_rows_per_sample : 1, ln_partials};
-    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, nullptr, dwd, B, H, W, E, target, gscale_dev, gscale, nb, stream);
+    return tulip_tail_bwd_dgrad_ln_c(xn, We, be, wd, dpred, dwd, B, H, W, E, target, gscale_dev, gscale, x, mean, rstd, gamma, dx,
+                                     dx_bf16, cast_rowscale, cast_rows_per_sample, ln_partials, stream, 1);
 }
 
-extern "C" int tulip_tail_fwd_ln(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
-                                 float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
-                                 const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
-                                 hipStream_t stream) {
+extern "C" int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+                                   float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                   const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
+                                   hipStream_t stream, int in_chans) {
     if (E <= 0 || (E & 7) || E > 128 || !x || !gamma || !beta || !xn || !mean || !rstd || !We || !be || !wd || !pred ||
-        (loss_partials && !target))
+        (loss_partials && !target) || bad_chans(in_chans))
         return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
@@ -809,11 +1016,22 @@ extern "C" int tulip_tail_fwd_ln(const float* x, const float* gamma, const float
     const TailNorm nrm{x, gamma, beta, eps, (bf16_t*)xn, mean, rstd};
     const TailLoss ls{target, loss_partials, log_transform};
     const int ks = (E + 31) / 32;
-    if (ks <= 2) hipLaunchKernelGGL(tail_fwd_ln_kernel<2>, grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls);
-    else if (ks == 3) hipLaunchKernelGGL(tail_fwd_ln_kernel<3>, grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls);
-    else hipLaunchKernelGGL(tail_fwd_ln_kernel<4>, grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls);
+#define TULIP_TFL(NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((tail_fwd_ln_kernel<2, NCH>), grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls); \
+    else if (ks == 3) hipLaunchKernelGGL((tail_fwd_ln_kernel<3, NCH>), grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls); \
+    else hipLaunchKernelGGL((tail_fwd_ln_kernel<4, NCH>), grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls);
+    TULIP_NCH_SWITCH(TULIP_TFL)
+#undef TULIP_TFL
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
+}
+
+extern "C" int tulip_tail_fwd_ln(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+                                 float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                 const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
+                                 hipStream_t stream) {
+    return tulip_tail_fwd_ln_c(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, target, loss_partials, log_transform, B, H, W,
+                               E, stream, 1);
 }
 
 // channels per workgroup of tulip_tail_wgrad: 8 waves x 3 (E % 24 == 0; 256 registers per wave) or 4 waves x 4; about one
@@ -835,10 +1053,11 @@ extern "C" int tulip_tail_wgrad_splits(int B, int H, int W, int E) {
     return sp;
 }
 
-extern "C" int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
-                                float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
-                                const float* gscale_dev, float gscale, hipStream_t stream) {
-    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !slabs_w || !slabs_b) return TULIP_ERR_ARG;
+extern "C" int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                                  float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
+                                  const float* gscale_dev, float gscale, hipStream_t stream, int in_chans) {
+    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !slabs_w || !slabs_b || bad_chans(in_chans))
+        return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     int ns, sp, st;
@@ -846,22 +1065,31 @@ extern "C" int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const fl
     const bool wide = E % 24 == 0;
     const dim3 grid(ns * sp), block(wide ? 512 : 256);
     const int wsh = (W >= 32 && (W & (W - 1)) == 0) ? 31 - __builtin_clz((unsigned)W) : -1;
-#define TULIP_TWG(KS, NB) \
-    do { if (wide) hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 3, 8>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+#define TULIP_TWG(KS, NB, NCH) \
+    do { if (wide) hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 3, 8, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
                        target, gscale_dev, gscale, slabs_w, slabs_b, g, ns, st, wsh); \
-         else hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 4, 4>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+         else hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 4, 4, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
                        target, gscale_dev, gscale, slabs_w, slabs_b, g, ns, st, wsh); } while (0)
-    switch (E / 16) {
-        case 1: TULIP_TWG(1, 1); break;
-        case 2: TULIP_TWG(1, 2); break;
-        case 3: TULIP_TWG(2, 3); break;
-        case 4: TULIP_TWG(2, 4); break;
-        case 5: TULIP_TWG(3, 5); break;
-        case 6: TULIP_TWG(3, 6); break;
-        case 7: TULIP_TWG(4, 7); break;
-        default: TULIP_TWG(4, 8); break;
+#define TULIP_TWG_E(NCH) \
+    switch (E / 16) { \
+        case 1: TULIP_TWG(1, 1, NCH); break; \
+        case 2: TULIP_TWG(1, 2, NCH); break; \
+        case 3: TULIP_TWG(2, 3, NCH); break; \
+        case 4: TULIP_TWG(2, 4, NCH); break; \
+        case 5: TULIP_TWG(3, 5, NCH); break; \
+        case 6: TULIP_TWG(3, 6, NCH); break; \
+        case 7: TULIP_TWG(4, 7, NCH); break; \
+        default: TULIP_TWG(4, 8, NCH); break; \
     }
+    TULIP_NCH_SWITCH(TULIP_TWG_E)
+#undef TULIP_TWG_E
 #undef TULIP_TWG
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
+}
+
+extern "C" int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                                float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
+                                const float* gscale_dev, float gscale, hipStream_t stream) {
+    return tulip_tail_wgrad_c(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target, gscale_dev, gscale, stream, 1);
 }

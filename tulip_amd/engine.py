@@ -349,7 +349,7 @@ class Plan:
             self.f32("tail.ey", maxM, r2 * E); self.f32("tail.emean", r2 * maxM); self.f32("tail.erstd", r2 * maxM)
         self.b16("tail.dxn", maxM, E)
         # partial-row workspaces of the atomic-free reductions
-        self.f32("tail.dwd_part", (maxM + 31) // 32, 128)
+        self.f32("tail.dwd_part", (maxM + 31) // 32, 128 * m.in_chans)      # [row][in_chans][128]
         W_ = eng.params
         o0 = W_.offset["patch_embed.proj.weight"]
         last = "patch_embed.norm.bias" if "patch_embed.norm.bias" in W_.offset else "patch_embed.proj.bias"
@@ -398,8 +398,18 @@ class TulipEngine:
         self.params: Optional[FlatParams] = None
         self.plans: Dict[int, Plan] = {}
         m = model
-        if m.in_chans != 1:
-            raise NotImplementedError("tulip_amd fused head supports in_chans == 1 (range images)")
+        # in_chans: the patch embedding's and the head's channel count (the kernels' NCH / Cin template parameter)
+        if not 1 <= m.in_chans <= 4:
+            raise NotImplementedError(f"tulip_amd supports in_chans 1 to 4 (got {m.in_chans}): the patch embedding and the "
+                                      f"fused head are instantiated for at most 4 image channels")
+        if m.in_chans > 1:
+            kw = 8 if m.circular_padding else m.patch_size[1]
+            taps = m.in_chans * m.patch_size[0] * kw
+            if taps > 16 and m.embed_dim not in (48, 96):
+                raise NotImplementedError(f"tulip_amd patch-embedding backward covers {taps} taps (in_chans * patch height * "
+                                          f"kernel width) only at embed_dim 48 or 96 (got {m.embed_dim})")
+            if not m.pixel_shuffle and m.embed_dim > 256:
+                raise NotImplementedError("tulip_amd FinalPatchExpanding with in_chans > 1 supports embed_dim <= 256")
         if m.upscale_factor != 4:
             raise NotImplementedError("tulip_amd fused head supports upscale_factor == 4 (every BASELINE config)")
         ws = m.window_size if isinstance(m.window_size, (tuple, list)) else (m.window_size, m.window_size)
@@ -1143,7 +1153,8 @@ class TulipEngine:
             ops.tail_fwd_ln(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), self.eps, P["tail.xn"], P["tail.mean"],
                             P["tail.rstd"], W_.p16("ps_head.conv_expand.0.weight"), W_.p32("ps_head.conv_expand.0.bias"),
                             W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, target=P.target if with_loss else None,
-                            loss_partials=P.partials if with_loss else None, log_transform=m.log_transform)
+                            loss_partials=P.partials if with_loss else None, log_transform=m.log_transform,
+                            in_chans=m.in_chans)
             if with_loss:
                 fin = lambda: ops.l1_loss_final(P.partials, P.losses, (M0 + 31) // 32, P.pred.numel(), m.log_transform)
                 if defer_loss_final:
@@ -1155,7 +1166,7 @@ class TulipEngine:
             ops.layernorm_fwd(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), P["tail.xn"], P["tail.mean"],
                               P["tail.rstd"], M0, E, self.eps)
             ops.tail_fwd(P["tail.xn"], W_.p16("ps_head.conv_expand.0.weight"), W_.p32("ps_head.conv_expand.0.bias"),
-                         W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E)
+                         W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, in_chans=m.in_chans)
         else:
             # FinalPatchExpanding (tulip.py:144-159) + decoder_pred (tulip.py:731): Linear E -> r^2 E, then one kernel
             # for rearrange + LayerNorm(E) + the 1x1 conv as a per-row dot product
@@ -1167,7 +1178,7 @@ class TulipEngine:
                        out=P["tail.ey"])
             ops.expand_norm_fwd(P["tail.ey"], W_.p32(pre + ".norm.weight"), W_.p32(pre + ".norm.bias"), P["tail.emean"],
                                 P["tail.erstd"], B, H0, W0, r, E, self.eps, dotw=W_.p32("decoder_pred.weight"),
-                                pred=P.pred)
+                                pred=P.pred, in_chans=m.in_chans)
         self._join_pack()                          # (a model without fused wide blocks never asked for the copies)
         if with_loss and not loss_done:
             ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform)
@@ -1865,7 +1876,8 @@ class TulipEngine:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
             targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred)
-            tkw = dict(target=P.target, gscale_dev=gscale_dev, gscale=gscale)   # L1 backward (tulip.py:692-693) formed in-kernel
+            tkw = dict(target=P.target, gscale_dev=gscale_dev, gscale=gscale,   # L1 backward (tulip.py:692-693) formed in-kernel
+                       in_chans=m.in_chans)
             self._tail_fused = self.fuse_tail_bwd and ops.tail_fused_bwd_supported(E)
             if self._tail_fused:
                 # d(expand pre-activation) -- 100 MB at batch 8 -- is never written: the chain's kernel goes straight to dxn,
@@ -1894,7 +1906,12 @@ class TulipEngine:
             else:
                 ops.tail_bwd(*targs, P["tail.dz"], tpart, B, H0, W0, E, **tkw)
                 self._wgrad(P["tail.dz"], 16 * E, P["tail.xn"], E, 16 * E, E, M0, G(head_w), G(head_b))
-            self._fold(tpart, 128, gdw, E, (M0 + 31) // 32)
+            if m.in_chans == 1:
+                self._fold(tpart, 128, gdw, E, (M0 + 31) // 32)
+            else:
+                # decoder_pred.weight (in_chans, E): channel k's gradient is columns [128 k, 128 k + E) of the partial rows
+                for k in range(m.in_chans):
+                    self._fold(tpart.data_ptr() + 4 * 128 * k, 128 * m.in_chans, gdw + 4 * E * k, E, (M0 + 31) // 32)
         else:
             # FinalPatchExpanding backward: d(pred) (L1, tulip.py:692-693) -> decoder_pred / LayerNorm backward per fine
             # token -> tail.dz = d(Linear output) in the Linear's layout
@@ -1902,13 +1919,14 @@ class TulipEngine:
             pre = "final_patch_expanding"
             ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
             R = ops.expand_norm_bwd_partial_rows(B, H0, W0, r)
-            part = P.scratch("exp.final", R * 3 * E)
+            nrow = (2 + m.in_chans) * E                 # [dgamma | dbeta | d(decoder_pred.weight) (in_chans, E)]
+            part = P.scratch("exp.final", R * nrow)
             ops.expand_norm_bwd(P["tail.ey"], P["tail.emean"], P["tail.erstd"], W_.p32(pre + ".norm.weight"), P["tail.dz"],
                                 part, B, H0, W0, r, E, dpred=P.dpred, dotw=W_.p32("decoder_pred.weight"),
-                                beta=W_.p32(pre + ".norm.bias"))
-            self._fold(part, 3 * E, G(pre + ".norm.weight"), E, R)
-            self._fold(part + 4 * E, 3 * E, G(pre + ".norm.bias"), E, R)
-            self._fold(part + 8 * E, 3 * E, gdw, E, R)
+                                beta=W_.p32(pre + ".norm.bias"), in_chans=m.in_chans)
+            self._fold(part, nrow, G(pre + ".norm.weight"), E, R)
+            self._fold(part + 4 * E, nrow, G(pre + ".norm.bias"), E, R)
+            self._fold(part + 8 * E, nrow, gdw, m.in_chans * E, R)
             head_w = pre + ".expand.weight"
             self._wgrad(P["tail.dz"], 16 * E, P["tail.xn"], E, 16 * E, E, M0, G(head_w))
         if not (m.pixel_shuffle and self._tail_fused):

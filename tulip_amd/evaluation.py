@@ -196,9 +196,17 @@ def _finish(table, args, log_writer, file_name: str, keys):
     return avg
 
 
+def _require_range_model(model):
+    """The metrics below are range-image metrics (one channel reshaped to H*W, projected to a point cloud)."""
+    c = getattr(model, "in_chans", 1)
+    if c != 1:
+        raise ValueError(f"evaluate / MCdrop compute range-image metrics and need in_chans == 1; this model has in_chans {c}")
+
+
 @torch.no_grad()
 def evaluate(data_loader, model, device, log_writer=None, args=None):
     """engine_upsampling.py:126-355.  Returns the averages it logs plus the per-image lists it saves."""
+    _require_range_model(model)
     ev = RangeEvaluator(args.dataset_select, args.img_size_low_res, args.img_size_high_res, args.log_transform,
                         args.grid_size, getattr(args, "keep_close_scan", False), False, device)
     model.eval()
@@ -227,6 +235,7 @@ def MCdrop(data_loader, model, device, log_writer=None, args=None):
     chamfer_dist only (:526-534).  As in the reference (:378-379) the model is put in eval mode and its Dropout modules back
     in train mode (enable_dropout): with p > 0 (TULIP(drop_rate=..., attn_drop_rate=...)) every pass draws its own masks;
     every reference configuration has p = 0, and then the passes are identical."""
+    _require_range_model(model)
     iteration, iteration_batch = args.num_mcdropout_iterations, 8
     assert iteration > iteration_batch                                                # :369
     ev = RangeEvaluator(args.dataset_select, args.img_size_low_res, args.img_size_high_res, args.log_transform,

@@ -26,7 +26,7 @@ class GraphedForward:
         return self.P.x_in
 
     @property
-    def pred(self) -> torch.Tensor:         # static output (B, 1, H, W)
+    def pred(self) -> torch.Tensor:         # static output (B, in_chans, H, W)
         return self.P.pred
 
     def weights_changed(self):

@@ -234,41 +234,42 @@ def cast_bf16_f32(x, y, n):
     check(_lib.load().tulip_cast_bf16_f32(_p(x), _p(y), n, _stream()), "tulip_cast_bf16_f32")
 
 
-def tail_fwd(xn, We, be, wd, pred, B, H, W, E):
-    check(_lib.load().tulip_tail_fwd(_p(xn), _p(We), _p(be), _p(wd), _p(pred), B, H, W, E, _stream()),
-          "tulip_tail_fwd")
+def tail_fwd(xn, We, be, wd, pred, B, H, W, E, in_chans=1):
+    check(_lib.load().tulip_tail_fwd_c(_p(xn), _p(We), _p(be), _p(wd), _p(pred), B, H, W, E, _stream(), int(in_chans)),
+          "tulip_tail_fwd_c")
 
 
-def tail_bwd(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0):
-    check(_lib.load().tulip_tail_bwd(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dz), _p(dwd), B, H, W, E,
-                                     _p(target), _p(gscale_dev), float(gscale), _stream()), "tulip_tail_bwd")
+def tail_bwd(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
+    check(_lib.load().tulip_tail_bwd_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dz), _p(dwd), B, H, W, E,
+                                       _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)), "tulip_tail_bwd_c")
 
 
 def tail_fused_bwd_supported(E):
     return bool(_lib.load().tulip_tail_fused_bwd_supported(int(E)))
 
 
-def tail_bwd_dgrad(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0):
+def tail_bwd_dgrad(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
     """Head backward on the chain: dxn (bf16 [M][E]) and the decoder_pred partial rows; d(expand) is never written."""
-    check(_lib.load().tulip_tail_bwd_dgrad(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dxn), _p(dwd), B, H, W, E,
-                                           _p(target), _p(gscale_dev), float(gscale), _stream()), "tulip_tail_bwd_dgrad")
+    check(_lib.load().tulip_tail_bwd_dgrad_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dxn), _p(dwd), B, H, W, E,
+                                             _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)),
+          "tulip_tail_bwd_dgrad_c")
 
 
 def tail_bwd_dgrad_ln(xn, We, be, wd, dpred, dwd, B, H, W, E, x, mean, rstd, gamma, dx, ln_partials, dx_bf16=None,
-                      cast_rowscale=None, cast_rows_per_sample=1, target=None, gscale_dev=None, gscale=1.0):
+                      cast_rowscale=None, cast_rows_per_sample=1, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
     """tail_bwd_dgrad with norm_up's backward in the epilogue: dx / dx_bf16 / [dgamma | dbeta] partial rows (one per 32 tokens)."""
-    check(_lib.load().tulip_tail_bwd_dgrad_ln(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dwd), B, H, W, E, _p(target),
-                                              _p(gscale_dev), float(gscale), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx),
-                                              _p(dx_bf16), _p(cast_rowscale), cast_rows_per_sample, _p(ln_partials),
-                                              _stream()), "tulip_tail_bwd_dgrad_ln")
+    check(_lib.load().tulip_tail_bwd_dgrad_ln_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dwd), B, H, W, E, _p(target),
+                                                _p(gscale_dev), float(gscale), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx),
+                                                _p(dx_bf16), _p(cast_rowscale), cast_rows_per_sample, _p(ln_partials),
+                                                _stream(), int(in_chans)), "tulip_tail_bwd_dgrad_ln_c")
 
 
 def tail_fwd_ln(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, B, H, W, E, target=None, loss_partials=None,
-                log_transform=False):
+                log_transform=False, in_chans=1):
     """norm_up + fused head (+ the L1 / pixel loss partial sums per 32 tokens) in one launch."""
-    check(_lib.load().tulip_tail_fwd_ln(_p(x), _p(gamma), _p(beta), float(eps), _p(xn), _p(mean), _p(rstd), _p(We), _p(be),
-                                        _p(wd), _p(pred), _p(target), _p(loss_partials), int(log_transform), B, H, W, E,
-                                        _stream()), "tulip_tail_fwd_ln")
+    check(_lib.load().tulip_tail_fwd_ln_c(_p(x), _p(gamma), _p(beta), float(eps), _p(xn), _p(mean), _p(rstd), _p(We), _p(be),
+                                          _p(wd), _p(pred), _p(target), _p(loss_partials), int(log_transform), B, H, W, E,
+                                          _stream(), int(in_chans)), "tulip_tail_fwd_ln_c")
 
 
 def l1_loss_final(partials, losses, nblocks, n, log_transform):
@@ -280,23 +281,25 @@ def tail_wgrad_splits(B, H, W, E):
     return _lib.load().tulip_tail_wgrad_splits(B, H, W, E)
 
 
-def tail_wgrad(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target=None, gscale_dev=None, gscale=1.0):
+def tail_wgrad(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
     """Expand-conv weight / bias gradient of the head as token-split slabs, d(expand) recomputed channel-sliced."""
-    check(_lib.load().tulip_tail_wgrad(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(slabs_w), _p(slabs_b), B, H, W, E,
-                                       _p(target), _p(gscale_dev), float(gscale), _stream()), "tulip_tail_wgrad")
+    check(_lib.load().tulip_tail_wgrad_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(slabs_w), _p(slabs_b), B, H, W, E,
+                                         _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)),
+          "tulip_tail_wgrad_c")
 
 
-def expand_norm_fwd(y, gamma, beta, mean, rstd, B, H, W, P, Cn, eps, out_bf16=None, ld=0, dotw=None, pred=None):
+def expand_norm_fwd(y, gamma, beta, mean, rstd, B, H, W, P, Cn, eps, out_bf16=None, ld=0, dotw=None, pred=None, in_chans=1):
     """PatchExpanding / FinalPatchExpanding rearrange + LayerNorm (+ decoder_pred dot), see include/tulip_hip.h."""
-    check(_lib.load().tulip_expand_norm_fwd(_p(y), _p(gamma), _p(beta), _p(out_bf16), ld, _p(dotw), _p(pred), _p(mean),
-                                            _p(rstd), B, H, W, P, Cn, eps, _stream()), "tulip_expand_norm_fwd")
+    check(_lib.load().tulip_expand_norm_fwd_c(_p(y), _p(gamma), _p(beta), _p(out_bf16), ld, _p(dotw), _p(pred), _p(mean),
+                                              _p(rstd), B, H, W, P, Cn, eps, _stream(), int(in_chans)), "tulip_expand_norm_fwd_c")
 
 
 def expand_norm_bwd(y, mean, rstd, gamma, dy_nat, partials, B, H, W, P, Cn, dy_fine=None, ld=0, dpred=None, dotw=None,
-                    beta=None):
-    check(_lib.load().tulip_expand_norm_bwd(_p(dy_fine), ld, _p(dpred), _p(dotw), _p(y), _p(mean), _p(rstd), _p(gamma),
-                                            _p(beta), _p(dy_nat), _p(partials), B, H, W, P, Cn, _stream()),
-          "tulip_expand_norm_bwd")
+                    beta=None, in_chans=1):
+    """partials: rows of [dgamma | dbeta | d(dotw) x in_chans] (stride (2 + in_chans) Cn, d(dotw) only with dotw)."""
+    check(_lib.load().tulip_expand_norm_bwd_c(_p(dy_fine), ld, _p(dpred), _p(dotw), _p(y), _p(mean), _p(rstd), _p(gamma),
+                                              _p(beta), _p(dy_nat), _p(partials), B, H, W, P, Cn, _stream(), int(in_chans)),
+          "tulip_expand_norm_bwd_c")
 
 
 def expand_norm_bwd_partial_rows(B, H, W, P):

@@ -295,6 +295,7 @@ def test_optimizer_step_in_the_weight_gradient_write_out_is_the_same_step(model,
     LayerNorm parameter pass (C > 2048), whose two ranges the overwrite mode has to clear itself."""
     import argparse
     import bench
+    from tests import adamw_audit as AA
     from tulip_amd.trainer import Trainer
     a = argparse.Namespace(model=model, img=list(img), target=list(target), batch=batch)
     res = []
@@ -305,8 +306,16 @@ def test_optimizer_step_in_the_weight_gradient_write_out_is_the_same_step(model,
         tr.fuse_adamw = tr.grad_overwrite = fuse
         lo, hi = bench.synthetic(a, 0, torch.device(DEV))
         tr.load_batch(lo, hi)
-        ls = torch.stack([tr.step().clone() for _ in range(8)])
+        snaps, ls = [AA.snapshot(tr)], []
+        for _ in range(8):
+            ls.append(tr.step().clone())
+            snaps.append(AA.snapshot(tr))
+        ls = torch.stack(ls)
         torch.cuda.synchronize()
+        # every step AdamW by its definition (an error both plans share passes the comparison below): with fuse the gradient of
+        # what the end-of-step launch steps stays in g; without, the launch clears it
+        bad = AA.audit_run(snaps, AA.layout_of(tr), [AA.Hyper(lr=5e-4, t=t) for t in range(1, 9)], "nonzero" if fuse else "unknown")
+        assert bad == [], (fuse, "\n".join(bad[:40]))
         W = tr.eng.params
         assert (tr.fused_adamw_params > 0.8 * sum(W.numel[n] for n in W.names)) == fuse
         res.append((W.flat.clone(), W.shadow.clone(), tr.m.clone(), tr.v.clone(), ls.cpu()))

@@ -91,6 +91,7 @@ def test_the_captured_step_is_reproducible_run_to_run():
     one register of one quarter-wave of `exp_avg` came out wrong a few times per thousand launches -- csrc/glue.hip WholeCU,
     tools/det_glue.py; this test is what would have caught it.)"""
     from tulip_amd.trainer import Trainer
+    from tests import adamw_audit as AA
     from tests.conftest import describe_flat_diff
     cfg = O.tulip_base_config()
     sd = O.key_seeded_state_dict(cfg, seed=5)
@@ -101,10 +102,15 @@ def test_the_captured_step_is_reproducible_run_to_run():
         m = build(cfg, sd, train=True)
         tr = Trainer(m, 8, lr=5e-4, betas=(0.9, 0.95), weight_decay=0.01)
         tr.load_batch(lo.to(DEV), hi.to(DEV))
+        snaps = [AA.snapshot(tr)]
         for _ in range(3):
             tr.step()
+            snaps.append(AA.snapshot(tr))
         torch.cuda.synchronize()
         got = (tr.eng.params.flat.clone(), tr.m.clone(), tr.v.clone())
+        # ... and every step of every run is AdamW (a deterministic error, or one that hits all six runs alike, shows here)
+        bad = AA.audit_run(snaps, AA.layout_of(tr), [AA.Hyper(lr=5e-4, t=t) for t in (1, 2, 3)], "nonzero")
+        assert bad == [], (rep, "\n".join(bad[:40]))
         if base is None:
             base = got
             continue

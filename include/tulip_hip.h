@@ -283,7 +283,7 @@ int tulip_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t stre
 
 /* Fused head (tulip.py:724-731): conv1x1 E->16E (+bias), LeakyReLU(0.01), PixelShuffle(4),
  * conv1x1 E->in_chans (no bias, wd [in_chans][E]); xn is norm_up's bf16 output [B*H*W][E]; pred is (B,in_chans,4H,4W)
- * fp32.  The (B,16E,H,W) intermediate (100 MB at B=8) is never materialised.  upscale factor 4.
+ * fp32.  The (B,16E,H,W) intermediate (100 MB at B=8) is never materialised.  upscale factor 4 (8: the _r forms below).
  * Every head entry point has a _c form with a trailing int in_chans (1 .. 4; anything else: TULIP_ERR_ARG); the form
  * without it is in_chans 1.  With in_chans > 1 the decoder_pred partial rows are [row][in_chans][128] and the L1
  * gradient divides by numel = in_chans * 16 * B*H*W. */
@@ -349,6 +349,36 @@ int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, co
 int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                        float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
                        const float* gscale_dev, float gscale, hipStream_t stream, int in_chans);
+/* Upscale factor r (PixelShuffle(r); tulip.py:577: r = int(sqrt(target area / image area)) * 2 * int(sqrt(patch area // 4)),
+ * 4 for patches of 4 .. 15 pixels, 8 for 16-pixel patches such as (2, 8) and (4, 4)).  Every head entry point has an _r form
+ * with trailing (int in_chans, int r), r in {4, 8} (anything else: TULIP_ERR_ARG, before any launch); the forms above are
+ * r = 4.  At r = 8 the expand conv is E -> 64E: We [64E][E], be [64E], output column oc = c*64 + i*8 + j (four MFMA column
+ * tiles per channel), pred / target / dpred are (B,in_chans,8H,8W), dz is [B*H*W][64E], the wgrad slabs are
+ * slabs_w[split][64E*E], slabs_b[split][64E] with tulip_tail_wgrad_splits_r(B,H,W,E,in_chans,r) splits, and the L1 gradient divides by
+ * numel = in_chans * 64 * B*H*W.  As at r = 4, only tulip_tail_bwd_r materialises the (B,r*r*E,H,W) gradient.  The partial
+ * rows (decoder_pred, norm_up, loss) keep their r = 4 layout: one row per 32 tokens. */
+int tulip_tail_fwd_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred, int B, int H,
+                     int W, int E, hipStream_t stream, int in_chans, int r);
+int tulip_tail_bwd_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                     uint16_t* dz, float* dwd_partials, int B, int H, int W, int E, const float* target,
+                     const float* gscale_dev, float gscale, hipStream_t stream, int in_chans, int r);
+int tulip_tail_fused_bwd_supported_r(int E, int r);
+int tulip_tail_bwd_dgrad_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                           uint16_t* dxn, float* dwd_partials, int B, int H, int W, int E, const float* target,
+                           const float* gscale_dev, float gscale, hipStream_t stream, int in_chans, int r);
+int tulip_tail_bwd_dgrad_ln_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                              float* dwd_partials, int B, int H, int W, int E, const float* target, const float* gscale_dev,
+                              float gscale, const float* x, const float* mean, const float* rstd, const float* gamma,
+                              float* dx, uint16_t* dx_bf16, const float* cast_rowscale, int cast_rows_per_sample,
+                              float* ln_partials, hipStream_t stream, int in_chans, int r);
+int tulip_tail_fwd_ln_r(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+                        float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred, const float* target,
+                        float* loss_partials, int log_transform, int B, int H, int W, int E, hipStream_t stream,
+                        int in_chans, int r);
+int tulip_tail_wgrad_splits_r(int B, int H, int W, int E, int in_chans, int r);
+int tulip_tail_wgrad_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                       float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
+                       const float* gscale_dev, float gscale, hipStream_t stream, int in_chans, int r);
 
 
 /* The non-default decoder alternates PatchExpanding (tulip.py:126-140, patch_unmerging=False; P = 2, Cn = C/2) and

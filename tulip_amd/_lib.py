@@ -156,6 +156,15 @@ SIGNATURES = {
     "tulip_tail_bwd_dgrad_ln_c": [P, P, P, P, P, P, I, I, I, I, P, P, F, P, P, P, P, P, P, P, I, P, P, I],
     "tulip_tail_fwd_ln_c": [P, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I],
     "tulip_tail_wgrad_c": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I],
+    # ... and with trailing (in_chans, r): the head at upscale_factor r in {4, 8}
+    "tulip_tail_fwd_r": [P, P, P, P, P, I, I, I, I, P, I, I],
+    "tulip_tail_bwd_r": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I, I],
+    "tulip_tail_fused_bwd_supported_r": [I, I],
+    "tulip_tail_bwd_dgrad_r": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I, I],
+    "tulip_tail_bwd_dgrad_ln_r": [P, P, P, P, P, P, I, I, I, I, P, P, F, P, P, P, P, P, P, P, I, P, P, I, I],
+    "tulip_tail_fwd_ln_r": [P, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I, I],
+    "tulip_tail_wgrad_splits_r": [I, I, I, I, I, I],
+    "tulip_tail_wgrad_r": [P, P, P, P, P, P, P, I, I, I, I, P, P, F, P, I, I],
     "tulip_expand_norm_fwd_c": [P, P, P, P, I, P, P, P, P, I, I, I, I, I, F, P, I],
     "tulip_expand_norm_bwd_c": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I],
     "tulip_l1_loss_fwd": [P, P, P, P, L, I, P],

@@ -617,7 +617,8 @@ __global__ __launch_bounds__(256) void patch_embed_bwd16_kernel(const float* __r
 
 bool embed_geom(EmbedGeom& g, int B, int Cin, int Hin, int Win, int E, int p0, int p1, int kw, int circular) {
     if (E <= 0 || E > 128 || p0 <= 0 || p1 <= 0 || Hin % p0 || Win % p1) return false;
-    if (circular && kw != p1 + 4) return false;   // kernel (p0, 8) over a (2,2)-padded row with stride 4 (tulip.py:41,60)
+    // circular: kernel (p0, 8), stride p1, over a (2,2)-padded row (tulip.py:41,60): W / p1 output columns for p1 = 4 and p1 = 8
+    if (circular && (kw != 8 || (p1 != 4 && p1 != 8))) return false;
     if (!circular && kw != p1) return false;
     g.B = B; g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.E = E; g.p0 = p0; g.p1 = p1; g.kw = kw; g.circular = circular;
     g.Ho = Hin / p0; g.Wo = Win / p1; g.taps = Cin * p0 * kw;

@@ -67,6 +67,13 @@ __device__ __forceinline__ size_t pred_off(const TailGeom& g, int tok, int i, in
     const int b = fast_div(t, g.H), h = t - b * g.H;
     return ((size_t)(b * NCH + k) * 4 * g.H + 4 * h + i) * (4 * g.W) + 4 * w;
 }
+// ... and of sub-row i (0 .. 7) of its 8x8 block at upscale_factor 8, pred (B, NCH, 8H, 8W)
+template <int NCH = 1>
+__device__ __forceinline__ size_t pred_off8(const TailGeom& g, int tok, int i, int k = 0) {
+    const int t = fast_div(tok, g.W), w = tok - t * g.W;
+    const int b = fast_div(t, g.H), h = t - b * g.H;
+    return ((size_t)(b * NCH + k) * 8 * g.H + 8 * h + i) * (8 * g.W) + 8 * w;
+}
 
 // f(id) for id = 0 .. N - 1 over a 256-thread workgroup: one guarded pass for N <= 256
 template <int N, class F>
@@ -431,7 +438,10 @@ struct TailNormBwd {
     const float* x; const float* mean; const float* rstd; const float* gamma;
     float* dx; bf16_t* dx_bf16; const float* cast_rowscale; int cast_rows_per_sample; float* param_partials;
 };
-template <int KS, int NB, int NCH>
+// UP = 8 (see tail8_fwd_kernel): wave q = wid takes tile q of every channel -- rows ((c*4 + q)*16 + li) of We, the pixels (row
+// 2q + (gq >> 1), columns 4 (gq & 1) ..) of its tokens -- so the four waves each hold a part of every channel's decoder_pred
+// gradient (lds_dwd gets a plane per wave, summed in a fixed order at the end); everything behind the channel loop is r = 4's
+template <int KS, int NB, int NCH, int UP = 4>
 __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                              const float* __restrict__ be, const float* __restrict__ wd,
                                                              const float* __restrict__ dpred, bf16_t* __restrict__ dxn,
@@ -441,27 +451,33 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
     constexpr int E = NB * 16, PITCH = tr_pitch(E), RP = E + 4;        // RP: fp32 row pitch of the cross-wave reduction
     constexpr int TILE = 32 * PITCH, RED = 32 * RP * 4;
     constexpr int MAIN = 4 * (TILE > RED ? TILE : RED);
-    __shared__ float lds_dwd[NCH * 128];
+    __shared__ float lds_dwd[(UP == 8 ? 4 : 1) * NCH * 128];
     // phase 1: four wave-private [32 output channels][E] tiles of We; phase 2 (overlaid): four [32 tokens][E] fp32 partial dxn;
     // behind them the [32 tokens][2E] LayerNorm affine-gradient terms of the fused norm_up backward
     __shared__ __attribute__((aligned(16))) unsigned char smem[MAIN + 32 * 2 * E * 4];
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
-    if constexpr (NCH == 1) { if (threadIdx.x < 128) lds_dwd[threadIdx.x] = 0.f; }
+    if constexpr (UP == 8) { for (int id = threadIdx.x; id < 4 * NCH * 128; id += 256) lds_dwd[id] = 0.f; }
+    else if constexpr (NCH == 1) { if (threadIdx.x < 128) lds_dwd[threadIdx.x] = 0.f; }
     else { for (int id = threadIdx.x; id < NCH * 128; id += 256) lds_dwd[id] = 0.f; }
     __syncthreads();
     const int m0 = blockIdx.x * 32;
     bf16x8 xb[2][KS];
     load_x<KS>(xn, g, m0, li, gq, xb);
+    // this lane's 4 pixels of plane k of token tok
+    auto pix = [&](int tok, int k) -> size_t {
+        if constexpr (UP == 8) return pred_off8<NCH>(g, tok, 2 * wid + (gq >> 1), k) + 4 * (gq & 1);
+        else return pred_off<NCH>(g, tok, gq, k);
+    };
     // NCH == 1: dp / dq = leaky_grad_sel's pair of the one upstream value; NCH > 1: dpk = the NCH upstream values, mixed per
     // expand channel c into sum_k wd[k][c] dpk[k] below
     float dp[2][4], dq[2][4], dpk[NCH][2][4];
-    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)(NCH * g.M));
+    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / ((float)(UP * UP) * (float)(NCH * g.M));
     if constexpr (NCH == 1) {
 #pragma unroll
         for (int mf = 0; mf < 2; ++mf) {
             const int tok = m0 + mf * 16 + li;
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (tok < g.M) d = pred_grad4(dpred, target, pred_off(g, tok, gq), gs);
+            if (tok < g.M) d = pred_grad4(dpred, target, pix(tok, 0), gs);
             dp[mf][0] = d.x; dp[mf][1] = d.y; dp[mf][2] = d.z; dp[mf][3] = d.w;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { dq[mf][r] = 0.495f * dp[mf][r]; dp[mf][r] *= 0.505f; }     // leaky_grad_sel's pair
@@ -473,11 +489,12 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
             for (int mf = 0; mf < 2; ++mf) {
                 const int tok = m0 + mf * 16 + li;
                 float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (tok < g.M) d = pred_grad4(dpred, target, pred_off<NCH>(g, tok, gq, k), gs);
+                if (tok < g.M) d = pred_grad4(dpred, target, pix(tok, k), gs);
                 dpk[k][mf][0] = d.x; dpk[k][mf][1] = d.y; dpk[k][mf][2] = d.z; dpk[k][mf][3] = d.w;
             }
     }
-    const int cper = g.E / 4, c0 = wid * cper, c1 = c0 + cper;          // E % 16 == 0: an even number of channels per wave
+    // E % 16 == 0: an even number of channels per wave (UP == 8: every wave walks all channels, its tile of each)
+    const int cper = UP == 8 ? g.E : g.E / 4, c0 = UP == 8 ? 0 : wid * cper, c1 = c0 + cper;
     unsigned char* tile = smem + wid * TILE;
     f32x4 dxa[NB][2];
 #pragma unroll
@@ -488,18 +505,19 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
             // rows c*16 .. +15 of We: A operand of the recomputed expand conv, and (through the tile) of the data gradient
+            const int vc = UP == 8 ? (c + cc) * 4 + wid : c + cc;
             bf16x8 wa[KS];
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const int k = ks * 32 + gq * 8;
                 bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
                 if (NB == 2 * KS || k < E) {              // (E == 32 KS at compile time: no branch around the load, see expand_channel)
-                    v = *(const bf16x8*)(We + (size_t)((c + cc) * 16 + li) * E + k);
+                    v = *(const bf16x8*)(We + (size_t)(vc * 16 + li) * E + k);
                     *(bf16x8*)(tile + (cc * 16 + li) * PITCH + k * 2) = v;
                 }
                 wa[ks] = v;
             }
-            const float4 b4 = *(const float4*)(be + (c + cc) * 16 + gq * 4);
+            const float4 b4 = *(const float4*)(be + vc * 16 + gq * 4);
             float wc[NCH];
 #pragma unroll
             for (int k = 0; k < NCH; ++k) wc[k] = wd[k * E + c + cc];
@@ -529,7 +547,13 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
                 }
                 ob[cc][mf] = pack4_t(o[0], o[1], o[2], o[3]);            // dz[token li][(c+cc)*16 + 4gq + r], bf16
             }
-            if constexpr (NCH == 1) {
+            if constexpr (UP == 8) {
+#pragma unroll
+                for (int k = 0; k < NCH; ++k) {
+                    part[k] = group_sum<64>(part[k]);
+                    if (lane == 0) lds_dwd[(wid * NCH + k) * 128 + c + cc] = part[k];
+                }
+            } else if constexpr (NCH == 1) {
                 const float pt = group_sum<64>(part[0]);
                 if (lane == 0) lds_dwd[c + cc] = pt;                      // channel c belongs to this wave alone
             } else {
@@ -630,11 +654,259 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_dgrad_kernel(const bf16_t* __
             }
         }
     }
-    if constexpr (NCH == 1) {
+    if constexpr (UP == 8) {
+        constexpr int PL = NCH * 128;
+        for (int id = threadIdx.x; id < PL; id += 256)
+            dwd[(size_t)blockIdx.x * PL + id] =
+                (id & 127) < g.E ? (lds_dwd[id] + lds_dwd[PL + id]) + (lds_dwd[2 * PL + id] + lds_dwd[3 * PL + id]) : 0.f;
+    } else if constexpr (NCH == 1) {
         if (threadIdx.x < 128) dwd[(size_t)blockIdx.x * 128 + threadIdx.x] = threadIdx.x < g.E ? lds_dwd[threadIdx.x] : 0.f;
     } else {
         for (int id = threadIdx.x; id < NCH * 128; id += 256) dwd[(size_t)blockIdx.x * (NCH * 128) + id] = (id & 127) < g.E ? lds_dwd[id] : 0.f;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// upscale_factor 8 (16-pixel patches: (2, 8), (4, 4)): the expand conv is [tokens x 64E x E], output column
+// oc = c*64 + (i*8 + j), a channel's 64 sub-pixels are FOUR MFMA column tiles q = 0 .. 3 (tile q = sub-rows i = 2q, 2q + 1).
+// Seen as 4E "virtual channels" vc = 4c + q of 16 columns each, the rows of We / be are addressed exactly as at r = 4
+// (row vc*16 + li).  Work split: a workgroup still owns 32 tokens, but wave q takes tile q of EVERY channel instead of a
+// quarter of the channels: lane (li, gq) then holds, summed over all c, the 4 pixels (row i = 2q + (gq >> 1), columns
+// 4 (gq & 1) .. + 3) of token li -- final values, so the forward has no cross-wave reduction and stores pred from registers
+// (16 B per lane, two lanes per 32-B row piece, 16 tokens = 512 contiguous bytes per image row).
+// rows vc*16 .. + 15 of We as the A operand (see expand_channel)
+template <int KS, bool FULL>
+__device__ __forceinline__ void load_w(const bf16_t* __restrict__ We, const TailGeom& g, int vc, int li, int gq, bf16x8 (&wa)[KS]) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int k = ks * 32 + gq * 8;
+        if constexpr (FULL) {
+            wa[ks] = *(const bf16x8*)(We + (size_t)(vc * 16 + li) * (KS * 32) + k);
+        } else {
+            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (k < g.E) v = *(const bf16x8*)(We + (size_t)(vc * 16 + li) * g.E + k);
+            wa[ks] = v;
+        }
+    }
+}
+
+// norm_up of the workgroup's 32 rows into the MFMA B fragments (the prologue of tail_fwd_ln_kernel)
+template <int KS>
+__device__ __forceinline__ void ln_rows(const TailNorm& nrm, const TailGeom& g, int m0, int li, int gq, int wid, bf16x8 (&xb)[2][KS]) {
+    const float invE = 1.0f / (float)g.E;
+#pragma unroll
+    for (int mf = 0; mf < 2; ++mf) {
+        const int tok = m0 + mf * 16 + li;
+        const bool valid = tok < g.M;
+        float v[KS][8];
+        float sm = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int k = ks * 32 + gq * 8;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (valid && k < g.E) {
+                a = *(const float4*)(nrm.x + (size_t)tok * g.E + k);
+                b = *(const float4*)(nrm.x + (size_t)tok * g.E + k + 4);
+            }
+            v[ks][0] = a.x; v[ks][1] = a.y; v[ks][2] = a.z; v[ks][3] = a.w;
+            v[ks][4] = b.x; v[ks][5] = b.y; v[ks][6] = b.z; v[ks][7] = b.w;
+            sm += ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w));
+        }
+        sm = rows_sum(sm);
+        const float mu = sm * invE;
+        float q = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            if (ks * 32 + gq * 8 < g.E) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float d = v[ks][e] - mu; q += d * d; }
+            }
+        q = rows_sum(q);
+        const float rs = rsqrtf(q * invE + nrm.eps);
+        if (wid == 0 && gq == 0 && valid) { nrm.mean[tok] = mu; nrm.rstd[tok] = rs; }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int k = ks * 32 + gq * 8;
+            bf16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (valid && k < g.E) {
+                const float4 g0 = *(const float4*)(nrm.gamma + k), g1 = *(const float4*)(nrm.gamma + k + 4);
+                const float4 b0 = *(const float4*)(nrm.beta + k), b1 = *(const float4*)(nrm.beta + k + 4);
+                const uint4 pk = make_uint4(
+                    pack_bf16x2((v[ks][0] - mu) * rs * g0.x + b0.x, (v[ks][1] - mu) * rs * g0.y + b0.y),
+                    pack_bf16x2((v[ks][2] - mu) * rs * g0.z + b0.z, (v[ks][3] - mu) * rs * g0.w + b0.w),
+                    pack_bf16x2((v[ks][4] - mu) * rs * g1.x + b1.x, (v[ks][5] - mu) * rs * g1.y + b1.y),
+                    pack_bf16x2((v[ks][6] - mu) * rs * g1.z + b1.z, (v[ks][7] - mu) * rs * g1.w + b1.w));
+                o = __builtin_bit_cast(bf16x8, pk);
+                if (wid == 0) *(uint4*)(nrm.xn + (size_t)tok * g.E + k) = pk;
+            }
+            xb[mf][ks] = o;
+        }
+    }
+}
+
+// r = 8 forward (LN: norm_up in front and the loss partials behind, as tail_fwd_ln_kernel).  A wave walks all E channels (the
+// same number of MFMAs per wave as four r = 4 workgroups' waves), a quarter of the workgroups of r = 4 at the same output image:
+// the rows of We are fetched UN channels ahead so that one wave per SIMD still hides the L2 latency.
+template <int KS, int NCH, bool LN>
+__global__ __launch_bounds__(256, 2) void tail8_fwd_kernel(const TailNorm nrm, const bf16_t* __restrict__ xn,
+                                                        const bf16_t* __restrict__ We, const float* __restrict__ be,
+                                                        const float* __restrict__ wd, float* __restrict__ pred, TailGeom g,
+                                                        const TailLoss ls) {
+    constexpr int UN = 4;                                                   // E % 8 == 0
+    __shared__ float lred[2][4];
+    const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
+    const int m0 = blockIdx.x * 32;
+    bf16x8 xb[2][KS];
+    if constexpr (LN) ln_rows<KS>(nrm, g, m0, li, gq, wid, xb);
+    else load_x<KS>(xn, g, m0, li, gq, xb);
+    float pacc[NCH][2][4] = {};
+    auto channels = [&](auto F) {
+        constexpr bool FULL = decltype(F)::value;
+        bf16x8 wcur[UN][KS], wnxt[UN][KS];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) load_w<KS, FULL>(We, g, u * 4 + wid, li, gq, wcur[u]);
+        for (int c = 0; c < g.E; c += UN) {
+            const int cn = min(c + UN, g.E - UN);                           // (the last group fetches itself again: loads stay unconditional)
+#pragma unroll
+            for (int u = 0; u < UN; ++u) load_w<KS, FULL>(We, g, (cn + u) * 4 + wid, li, gq, wnxt[u]);
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int vc = (c + u) * 4 + wid;
+                const float4 b4 = *(const float4*)(be + vc * 16 + gq * 4);
+                float wc[NCH];
+#pragma unroll
+                for (int k = 0; k < NCH; ++k) wc[k] = wd[k * g.E + c + u];
+                const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+                for (int mf = 0; mf < 2; ++mf) {
+                    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[u][ks], xb[mf][ks], a, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {                           // a[r] = Z[token li of frag mf][vc*16 + 4*gq + r]
+                        const float lz = leaky01(a[r] + bb[r]);
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) pacc[k][mf][r] += wc[k] * lz;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UN; ++u)
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) wcur[u][ks] = wnxt[u][ks];
+        }
+    };
+    if (g.E == KS * 32) channels(std::true_type{}); else channels(std::false_type{});      // (uniform)
+    const int pi = 2 * wid + (gq >> 1), pj = 4 * (gq & 1);                 // this lane's pixel row and first column inside the 8x8 block
+    float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf) {
+            const int tok = m0 + mf * 16 + li;
+            if (tok < g.M) {
+                const float4 o = make_float4(pacc[k][mf][0], pacc[k][mf][1], pacc[k][mf][2], pacc[k][mf][3]);
+                const size_t po = pred_off8<NCH>(g, tok, pi, k) + pj;
+                *(float4*)(pred + po) = o;
+                if (LN && ls.partials) {
+                    const float4 q = *(const float4*)(ls.target + po);
+                    l0 += (fabsf(o.x - q.x) + fabsf(o.y - q.y)) + (fabsf(o.z - q.z) + fabsf(o.w - q.w));
+                    if (ls.log_transform)
+                        l1 += (fabsf(expm1f(o.x) - expm1f(q.x)) + fabsf(expm1f(o.y) - expm1f(q.y))) +
+                              (fabsf(expm1f(o.z) - expm1f(q.z)) + fabsf(expm1f(o.w) - expm1f(q.w)));
+                }
+            }
+        }
+    if (LN && ls.partials) {                                                // uniform
+        l0 = group_sum<64>(l0); l1 = group_sum<64>(l1);
+        if (lane == 0) { lred[0][wid] = l0; lred[1][wid] = l1; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            ls.partials[blockIdx.x * 2] = (lred[0][0] + lred[0][1]) + (lred[0][2] + lred[0][3]);
+            ls.partials[blockIdx.x * 2 + 1] = (lred[1][0] + lred[1][1]) + (lred[1][2] + lred[1][3]);
+        }
+    }
+}
+
+// r = 8 form of tail_bwd_kernel: dz[M][64E].  Wave q writes, per token and channel, the 32-B piece of its tile (columns
+// c*64 + q*16 .. + 15) through the wave-private tile, four channels at a time; the decoder_pred partial of a channel is the
+// sum of the four waves' parts (fixed order)
+template <int KS, int NCH>
+__global__ __launch_bounds__(256, 2) void tail8_bwd_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
+                                                        const float* __restrict__ be, const float* __restrict__ wd,
+                                                        const float* __restrict__ dpred, bf16_t* __restrict__ dz,
+                                                        float* dwd, TailGeom g, const float* __restrict__ target,
+                                                        const float* __restrict__ gscale_dev, float gscale) {
+    __shared__ float lds_dwd[4][NCH * 128];
+    __shared__ __attribute__((aligned(16))) bf16_t stile[4][32 * 72];   // 64 cols + 8 pad (bank spread)
+    const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
+    for (int id = threadIdx.x; id < 4 * NCH * 128; id += 256) (&lds_dwd[0][0])[id] = 0.f;
+    __syncthreads();
+    const int m0 = blockIdx.x * 32;
+    bf16x8 xb[2][KS];
+    load_x<KS>(xn, g, m0, li, gq, xb);
+    const int pi = 2 * wid + (gq >> 1), pj = 4 * (gq & 1);
+    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (64.0f * (float)(NCH * g.M));
+    float dp[NCH][2][4];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf) {
+            const int tok = m0 + mf * 16 + li;
+            float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tok < g.M) d = pred_grad4(dpred, target, pred_off8<NCH>(g, tok, pi, k) + pj, gs);
+            dp[k][mf][0] = d.x; dp[k][mf][1] = d.y; dp[k][mf][2] = d.z; dp[k][mf][3] = d.w;
+        }
+    const int N = 64 * g.E;
+    bf16_t* tile = stile[wid];
+    for (int cg = 0; cg < g.E; cg += 4) {                                   // E % 8 == 0
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            const int c = cg + cc, vc = c * 4 + wid;
+            f32x4 acc[2];
+            expand_channel<KS>(We, g, vc, li, gq, xb, acc);
+            const float4 b4 = *(const float4*)(be + vc * 16 + gq * 4);
+            float wc[NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) wc[k] = wd[k * g.E + c];
+            const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+            float part[NCH] = {};
+#pragma unroll
+            for (int mf = 0; mf < 2; ++mf) {
+                float o[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float z = acc[mf][r] + bb[r];
+                    const bool pos = z > 0.f;
+                    float u = dp[0][mf][r] * wc[0];
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        part[k] += dp[k][mf][r] * (pos ? z : 0.01f * z);
+                        if (k > 0) u += dp[k][mf][r] * wc[k];
+                    }
+                    o[r] = u * (pos ? 1.0f : 0.01f);
+                }
+                *(uint2*)(tile + (mf * 16 + li) * 72 + cc * 16 + gq * 4) =
+                    make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+            }
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                part[k] = group_sum<64>(part[k]);
+                if (lane == 0) lds_dwd[wid][k * 128 + c] = part[k];
+            }
+        }
+        // wave-private tile: LDS ops of one wave execute in order, no barrier needed.  8 16-B chunks per token row
+        for (int id = lane; id < 32 * 8; id += 64) {
+            const int t = id >> 3, ch = id & 7;                              // chunk ch: channel cg + (ch >> 1), half ch & 1
+            const int tok = m0 + t;
+            if (tok < g.M)
+                *(uint4*)(dz + (size_t)tok * N + (cg + (ch >> 1)) * 64 + wid * 16 + (ch & 1) * 8) = *(const uint4*)(tile + t * 72 + ch * 8);
+        }
+    }
+    __syncthreads();
+    for (int id = threadIdx.x; id < NCH * 128; id += 256)
+        dwd[(size_t)blockIdx.x * (NCH * 128) + id] =
+            (id & 127) < g.E ? (lds_dwd[0][id] + lds_dwd[1][id]) + (lds_dwd[2][id] + lds_dwd[3][id]) : 0.f;
 }
 
 template <int N, class F>
@@ -648,23 +920,28 @@ __device__ __forceinline__ void static_for_t(F&& f) {
 //
 // NCH > 1: dz of expand channel c is leaky'(z) sum_k wd[k][c] dpred_k, a different mix per channel, so the mix is formed in front
 // of the MFMAs (it cannot be factored out as the single decoder_pred weight is at NCH == 1) and pred / target hold NCH planes
-template <int KS, int NB, int NC, int NWV, int NCH>
+//
+// UP = 8: the 4E virtual channels vc = 4c + q (16 output columns each, see tail8_fwd_kernel) are sliced exactly as the E channels
+// of r = 4 -- rows vc*16 + li of We, be and of the slabs -- with decoder_pred weight wd[vc >> 2]; a token's pred / target piece is
+// 8 rows x 2 float4 per plane, and the lane's sub-pixel is (vc & 3)*16 + li, so it is read from the step's tile per channel
+template <int KS, int NB, int NC, int NWV, int NCH, int UP = 4>
 __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_wgrad_kernel(const bf16_t* __restrict__ xn, const bf16_t* __restrict__ We,
                                                       const float* __restrict__ be, const float* __restrict__ wd,
                                                       const float* __restrict__ dpred, const float* __restrict__ target,
                                                       const float* __restrict__ gscale_dev, float gscale,
                                                       float* __restrict__ slab_w, float* __restrict__ slab_b, TailGeom g,
                                                       int nslices, int steps_per_split, int wshift) {
-    constexpr int NT = 64 * NWV, PD = (128 * NCH + NT - 1) / NT;        // PD: pred pieces per thread (one channel plane each)
+    constexpr int PP = UP == 8 ? 512 : 128;                               // float4 pred pieces of a 32-token step, per plane
+    constexpr int NT = 64 * NWV, PD = (PP * NCH + NT - 1) / NT;         // PD: pred pieces per thread (one channel plane each)
     constexpr int E = NB * 16, PITCH = tr_pitch(E), CPR = E / 8, NCHUNK = 32 * CPR, PER = (NCHUNK + NT - 1) / NT;
     __shared__ __attribute__((aligned(16))) unsigned char xt[2][32 * PITCH];
-    __shared__ __attribute__((aligned(16))) float dpt[2][NCH][16][36];     // [channel][sub-pixel][token], rows padded to 144 B
+    __shared__ __attribute__((aligned(16))) float dpt[2][NCH][UP * UP][36];  // [channel][sub-pixel][token], rows padded to 144 B
     const int lane = threadIdx.x & 63, li = lane & 15, gq = lane >> 4, wid = threadIdx.x >> 6;
     const int slice = blockIdx.x % nslices, split = blockIdx.x / nslices;
     const int cb = (slice * NWV + wid) * NC;                               // nslices = E / (NWV NC)
     const int total = (g.M + 31) >> 5;
     const int s0 = split * steps_per_split, s1 = min(total, s0 + steps_per_split);
-    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / (16.0f * (float)(NCH * g.M));
+    const float gs = (gscale_dev ? gscale_dev[0] : gscale) / ((float)(UP * UP) * (float)(NCH * g.M));
     // this wave's rows of We as B operands (column = output channel li of channel cb + cc), its bias and decoder weights
     bf16x8 wb[NC][KS];
     float bev[NC], wdv[NCH][NC];
@@ -679,7 +956,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
         }
         bev[cc] = be[(cb + cc) * 16 + li];
 #pragma unroll
-        for (int k = 0; k < NCH; ++k) wdv[k][cc] = wd[k * E + cb + cc];
+        for (int k = 0; k < NCH; ++k) wdv[k][cc] = wd[k * E + (UP == 8 ? (cb + cc) >> 2 : cb + cc)];
     }
     f32x4 acc[NC][NB];
     float bsum[NC];
@@ -724,7 +1001,15 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
             if (!full) off = (unsigned)min(xrow[i], g.M - 1 - m0) * (E * 2) + xcol[i];
             xr[r][i] = *(const u32x4_s*)(xb + off);
         }
-        if constexpr (NCH == 1) {
+        if constexpr (UP == 8) {
+#pragma unroll
+            for (int j = 0; j < PD; ++j) {                                     // piece id: plane id >> 9, token, row, half (clamped: loads are unconditional)
+                const int id = min((int)threadIdx.x + j * NT, PP * NCH - 1), pp = id & 511;
+                const unsigned po = (unsigned)(pred_off8<NCH>(g, min(m0 + (pp >> 4), g.M - 1), (pp >> 1) & 7, id >> 9) + 4 * (pp & 1));
+                dr[r][j] = *(const float4*)(dpred + po);
+                tr[r][j] = *(const float4*)(tsrc + po);
+            }
+        } else if constexpr (NCH == 1) {
             unsigned po;
             if (wshift >= 0 && full) po = (unsigned)(16 * (m0 >> wshift) * g.W + 4 * (m0 & (g.W - 1))) + ppix;
             else po = (unsigned)pred_off(g, min(m0 + pt, g.M - 1), pi);
@@ -753,7 +1038,24 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
                 *(u32x4_s*)(xt[buf] + t * PITCH + k8 * 16) = v;
             }
         }
-        if constexpr (NCH == 1) {
+        if constexpr (UP == 8) {
+#pragma unroll
+            for (int j = 0; j < PD; ++j) {
+                const int id = threadIdx.x + j * NT, pp = id & 511, t8 = pp >> 4;
+                if ((PP * NCH) % NT == 0 || id < PP * NCH) {
+                    float4 d = dr[r][j];
+                    if (target) {
+                        const float4 q = tr[r][j];
+                        const float e[4] = {d.x - q.x, d.y - q.y, d.z - q.z, d.w - q.w};
+                        d = make_float4(e[0] > 0.f ? gs : (e[0] < 0.f ? -gs : 0.f), e[1] > 0.f ? gs : (e[1] < 0.f ? -gs : 0.f),
+                                        e[2] > 0.f ? gs : (e[2] < 0.f ? -gs : 0.f), e[3] > 0.f ? gs : (e[3] < 0.f ? -gs : 0.f));
+                    }
+                    if (m0 + t8 >= g.M) d = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float (*dk)[36] = dpt[buf][id >> 9] + (((pp >> 1) & 7) * 8 + (pp & 1) * 4);   // sub-pixel = row * 8 + column
+                    dk[0][t8] = d.x; dk[1][t8] = d.y; dk[2][t8] = d.z; dk[3][t8] = d.w;
+                }
+            }
+        } else if constexpr (NCH == 1) {
             if (threadIdx.x < 128) {
                 float4 d = dr[r][0];
                 if (target) {
@@ -802,10 +1104,11 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
             // the upstream gradient of this lane's sub-pixel li at its 2 x 4 tokens, as the pair leaky_grad_sel takes
             // (NCH > 1: the raw values of every plane, mixed per channel below)
             float dpl[2][4], dql[2][4], dk[NCH][2][4];
+            auto load_dp = [&](int sp) {
             if constexpr (NCH == 1) {
 #pragma unroll
                 for (int mf = 0; mf < 2; ++mf) {
-                    const float4 d = *(const float4*)&dpt[buf][0][li][mf * 16 + 4 * gq];
+                    const float4 d = *(const float4*)&dpt[buf][0][sp][mf * 16 + 4 * gq];
                     dpl[mf][0] = d.x; dpl[mf][1] = d.y; dpl[mf][2] = d.z; dpl[mf][3] = d.w;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { dql[mf][r] = 0.495f * dpl[mf][r]; dpl[mf][r] *= 0.505f; }   // leaky_grad_sel's pair
@@ -815,12 +1118,15 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
                 for (int k = 0; k < NCH; ++k)
 #pragma unroll
                     for (int mf = 0; mf < 2; ++mf) {
-                        const float4 d = *(const float4*)&dpt[buf][k][li][mf * 16 + 4 * gq];
+                        const float4 d = *(const float4*)&dpt[buf][k][sp][mf * 16 + 4 * gq];
                         dk[k][mf][0] = d.x; dk[k][mf][1] = d.y; dk[k][mf][2] = d.z; dk[k][mf][3] = d.w;
                     }
             }
+            };
+            if constexpr (UP != 8) load_dp(li);
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) {
+                if constexpr (UP == 8) load_dp(((cb + cc) & 3) * 16 + li);
                 bf16x4 ob[2];
 #pragma unroll
                 for (int mf = 0; mf < 2; ++mf) {
@@ -866,8 +1172,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
     for (int s = s0; s < s1; s += RING)
         static_for_t<RING>([&](auto J) { if (s + decltype(J)::value < s1) step(J, s + decltype(J)::value); });
     // acc[cc][n][r] = dWe[(cb+cc)*16 + li][16n + 4gq + r]: one plain slab per token split, folded by tulip_reduce_rows_multi
-    float* ow = slab_w + (size_t)split * (16 * E) * E;
-    float* ob_ = slab_b + (size_t)split * (16 * E);
+    float* ow = slab_w + (size_t)split * (UP * UP * E) * E;
+    float* ob_ = slab_b + (size_t)split * (UP * UP * E);
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) {
         const int oc = (cb + cc) * 16 + li;
@@ -889,14 +1195,29 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 && NC <= 2 ? 2 : 1)) void tail_
     switch (in_chans) { case 1: X(1); break; case 2: X(2); break; case 3: X(3); break; default: X(4); break; }
 
 static bool bad_chans(int in_chans) { return in_chans < 1 || in_chans > 4; }
+// r: the head's upscale factor (PixelShuffle(r)), 4 or 8.  Every entry point has an _r form with trailing (in_chans, r); the
+// _c forms and the plain ones are r = 4 and launch what they always launched
+static bool bad_r(int r) { return r != 4 && r != 8; }
 
-extern "C" int tulip_tail_fwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
-                                int B, int H, int W, int E, hipStream_t stream, int in_chans) {
-    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans)) return TULIP_ERR_ARG;
+extern "C" int tulip_tail_fwd_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                int B, int H, int W, int E, hipStream_t stream, int in_chans, int r) {
+    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans) || bad_r(r)) return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     const dim3 grid((g.M + 31) / 32), block(256);
     const int ks = (E + 31) / 32;
+    if (r == 8) {
+        const TailNorm nrm{nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr};
+        const TailLoss ls{nullptr, nullptr, 0};
+#define TULIP_TF8(NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((tail8_fwd_kernel<2, NCH, false>), grid, block, 0, stream, nrm, xn, We, be, wd, pred, g, ls); \
+    else if (ks == 3) hipLaunchKernelGGL((tail8_fwd_kernel<3, NCH, false>), grid, block, 0, stream, nrm, xn, We, be, wd, pred, g, ls); \
+    else hipLaunchKernelGGL((tail8_fwd_kernel<4, NCH, false>), grid, block, 0, stream, nrm, xn, We, be, wd, pred, g, ls);
+        TULIP_NCH_SWITCH(TULIP_TF8)
+#undef TULIP_TF8
+        TULIP_CHECK_LAUNCH();
+        return TULIP_OK;
+    }
 #define TULIP_TF(NCH) \
     if (ks <= 2) hipLaunchKernelGGL((tail_fwd_kernel<2, NCH>), grid, block, 0, stream, xn, We, be, wd, pred, g); \
     else if (ks == 3) hipLaunchKernelGGL((tail_fwd_kernel<3, NCH>), grid, block, 0, stream, xn, We, be, wd, pred, g); \
@@ -907,47 +1228,68 @@ extern "C" int tulip_tail_fwd_c(const uint16_t* xn, const uint16_t* We, const fl
     return TULIP_OK;
 }
 
+extern "C" int tulip_tail_fwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                int B, int H, int W, int E, hipStream_t stream, int in_chans) {
+    return tulip_tail_fwd_r(xn, We, be, wd, pred, B, H, W, E, stream, in_chans, 4);
+}
+
 extern "C" int tulip_tail_fwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, float* pred,
                               int B, int H, int W, int E, hipStream_t stream) {
-    return tulip_tail_fwd_c(xn, We, be, wd, pred, B, H, W, E, stream, 1);
+    return tulip_tail_fwd_r(xn, We, be, wd, pred, B, H, W, E, stream, 1, 4);
+}
+
+extern "C" int tulip_tail_bwd_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                const float* dpred, uint16_t* dz, float* dwd, int B, int H, int W, int E,
+                                const float* target, const float* gscale_dev, float gscale, hipStream_t stream, int in_chans,
+                                int r) {
+    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans) || bad_r(r)) return TULIP_ERR_ARG;
+    TailGeom g{B * H * W, H, W, E};
+    if (g.M <= 0) return TULIP_OK;
+    const dim3 grid((g.M + 31) / 32), block(256);
+    const int ks = (E + 31) / 32;
+#define TULIP_TB_K(K, NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((K<2, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
+    else if (ks == 3) hipLaunchKernelGGL((K<3, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
+    else hipLaunchKernelGGL((K<4, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
+#define TULIP_TB(NCH) TULIP_TB_K(tail_bwd_kernel, NCH)
+#define TULIP_TB8(NCH) TULIP_TB_K(tail8_bwd_kernel, NCH)
+    if (r == 8) { TULIP_NCH_SWITCH(TULIP_TB8) }
+    else { TULIP_NCH_SWITCH(TULIP_TB) }
+#undef TULIP_TB8
+#undef TULIP_TB
+#undef TULIP_TB_K
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
 }
 
 extern "C" int tulip_tail_bwd_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                                 const float* dpred, uint16_t* dz, float* dwd, int B, int H, int W, int E,
                                 const float* target, const float* gscale_dev, float gscale, hipStream_t stream, int in_chans) {
-    if (E <= 0 || (E & 7) || E > 128 || bad_chans(in_chans)) return TULIP_ERR_ARG;
-    TailGeom g{B * H * W, H, W, E};
-    if (g.M <= 0) return TULIP_OK;
-    const dim3 grid((g.M + 31) / 32), block(256);
-    const int ks = (E + 31) / 32;
-#define TULIP_TB(NCH) \
-    if (ks <= 2) hipLaunchKernelGGL((tail_bwd_kernel<2, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
-    else if (ks == 3) hipLaunchKernelGGL((tail_bwd_kernel<3, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale); \
-    else hipLaunchKernelGGL((tail_bwd_kernel<4, NCH>), grid, block, 0, stream, xn, We, be, wd, dpred, dz, dwd, g, target, gscale_dev, gscale);
-    TULIP_NCH_SWITCH(TULIP_TB)
-#undef TULIP_TB
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return tulip_tail_bwd_r(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target, gscale_dev, gscale, stream, in_chans, 4);
 }
 
 extern "C" int tulip_tail_bwd(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                               const float* dpred, uint16_t* dz, float* dwd, int B, int H, int W, int E,
                               const float* target, const float* gscale_dev, float gscale, hipStream_t stream) {
-    return tulip_tail_bwd_c(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1);
+    return tulip_tail_bwd_r(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1, 4);
 }
 
 extern "C" int tulip_tail_fused_bwd_supported(int E) { return E > 0 && E % 16 == 0 && E <= 128; }
+extern "C" int tulip_tail_fused_bwd_supported_r(int E, int r) { return !bad_r(r) && tulip_tail_fused_bwd_supported(E); }
 
 static int tail_bwd_dgrad_impl(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                                uint16_t* dxn, float* dwd, int B, int H, int W, int E, const float* target,
-                               const float* gscale_dev, float gscale, const TailNormBwd& nb, hipStream_t stream, int in_chans) {
-    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !dwd || bad_chans(in_chans)) return TULIP_ERR_ARG;
+                               const float* gscale_dev, float gscale, const TailNormBwd& nb, hipStream_t stream, int in_chans,
+                               int r) {
+    if (!tulip_tail_fused_bwd_supported_r(E, r) || !xn || !We || !be || !wd || !dpred || !dwd || bad_chans(in_chans)) return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     const dim3 grid((g.M + 31) / 32), block(256);
 #define TULIP_TBD(KS, NB, NCH) \
-    hipLaunchKernelGGL((tail_bwd_dgrad_kernel<KS, NB, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
-                       (bf16_t*)dxn, dwd, g, target, gscale_dev, gscale, nb)
+    do { if (r == 8) hipLaunchKernelGGL((tail_bwd_dgrad_kernel<KS, NB, NCH, 8>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+                       (bf16_t*)dxn, dwd, g, target, gscale_dev, gscale, nb); \
+         else hipLaunchKernelGGL((tail_bwd_dgrad_kernel<KS, NB, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+                       (bf16_t*)dxn, dwd, g, target, gscale_dev, gscale, nb); } while (0)
 #define TULIP_TBD_E(NCH) \
     switch (E / 16) { \
         case 1: TULIP_TBD(1, 1, NCH); break; \
@@ -966,19 +1308,38 @@ static int tail_bwd_dgrad_impl(const uint16_t* xn, const uint16_t* We, const flo
     return TULIP_OK;
 }
 
+extern "C" int tulip_tail_bwd_dgrad_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                      const float* dpred, uint16_t* dxn, float* dwd, int B, int H, int W, int E,
+                                      const float* target, const float* gscale_dev, float gscale, hipStream_t stream,
+                                      int in_chans, int r) {
+    if (!dxn) return TULIP_ERR_ARG;
+    const TailNormBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr};
+    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, none, stream, in_chans, r);
+}
+
 extern "C" int tulip_tail_bwd_dgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                                       const float* dpred, uint16_t* dxn, float* dwd, int B, int H, int W, int E,
                                       const float* target, const float* gscale_dev, float gscale, hipStream_t stream,
                                       int in_chans) {
-    if (!dxn) return TULIP_ERR_ARG;
-    const TailNormBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr};
-    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, none, stream, in_chans);
+    return tulip_tail_bwd_dgrad_r(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, stream, in_chans, 4);
 }
 
 extern "C" int tulip_tail_bwd_dgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
                                     const float* dpred, uint16_t* dxn, float* dwd, int B, int H, int W, int E,
                                     const float* target, const float* gscale_dev, float gscale, hipStream_t stream) {
-    return tulip_tail_bwd_dgrad_c(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1);
+    return tulip_tail_bwd_dgrad_r(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target, gscale_dev, gscale, stream, 1, 4);
+}
+
+extern "C" int tulip_tail_bwd_dgrad_ln_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
+                                         const float* dpred, float* dwd, int B, int H, int W, int E, const float* target,
+                                         const float* gscale_dev, float gscale, const float* x, const float* mean,
+                                         const float* rstd, const float* gamma, float* dx, uint16_t* dx_bf16,
+                                         const float* cast_rowscale, int cast_rows_per_sample, float* ln_partials,
+                                         hipStream_t stream, int in_chans, int r) {
+    if (!x || !mean || !rstd || !gamma || !dx) return TULIP_ERR_ARG;
+    const TailNormBwd nb{x, mean, rstd, gamma, dx, (bf16_t*)dx_bf16, cast_rowscale,
+                         cast_rows_per_sample > 0 ? cast_rows_per_sample : 1, ln_partials};
+    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, nullptr, dwd, B, H, W, E, target, gscale_dev, gscale, nb, stream, in_chans, r);
 }
 
 extern "C" int tulip_tail_bwd_dgrad_ln_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
@@ -987,10 +1348,8 @@ extern "C" int tulip_tail_bwd_dgrad_ln_c(const uint16_t* xn, const uint16_t* We,
                                          const float* rstd, const float* gamma, float* dx, uint16_t* dx_bf16,
                                          const float* cast_rowscale, int cast_rows_per_sample, float* ln_partials,
                                          hipStream_t stream, int in_chans) {
-    if (!x || !mean || !rstd || !gamma || !dx) return TULIP_ERR_ARG;
-    const TailNormBwd nb{x, mean, rstd, gamma, dx, (bf16_t*)dx_bf16, cast_rowscale,
-                         cast_rows_per_sample > 0 ? cast_rows_per_sample : 1, ln_partials};
-    return tail_bwd_dgrad_impl(xn, We, be, wd, dpred, nullptr, dwd, B, H, W, E, target, gscale_dev, gscale, nb, stream, in_chans);
+    return tulip_tail_bwd_dgrad_ln_r(xn, We, be, wd, dpred, dwd, B, H, W, E, target, gscale_dev, gscale, x, mean, rstd, gamma, dx,
+                                     dx_bf16, cast_rowscale, cast_rows_per_sample, ln_partials, stream, in_chans, 4);
 }
 
 extern "C" int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd,
@@ -999,16 +1358,16 @@ extern "C" int tulip_tail_bwd_dgrad_ln(const uint16_t* xn, const uint16_t* We, c
                                        const float* rstd, const float* gamma, float* dx, uint16_t* dx_bf16,
                                        const float* cast_rowscale, int cast_rows_per_sample, float* ln_partials,
                                        hipStream_t stream) {
-    return tulip_tail_bwd_dgrad_ln_c(xn, We, be, wd, dpred, dwd, B, H, W, E, target, gscale_dev, gscale, x, mean, rstd, gamma, dx,
-                                     dx_bf16, cast_rowscale, cast_rows_per_sample, ln_partials, stream, 1);
+    return tulip_tail_bwd_dgrad_ln_r(xn, We, be, wd, dpred, dwd, B, H, W, E, target, gscale_dev, gscale, x, mean, rstd, gamma, dx,
+                                     dx_bf16, cast_rowscale, cast_rows_per_sample, ln_partials, stream, 1, 4);
 }
 
-extern "C" int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+extern "C" int tulip_tail_fwd_ln_r(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
                                    float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
                                    const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
-                                   hipStream_t stream, int in_chans) {
+                                   hipStream_t stream, int in_chans, int r) {
     if (E <= 0 || (E & 7) || E > 128 || !x || !gamma || !beta || !xn || !mean || !rstd || !We || !be || !wd || !pred ||
-        (loss_partials && !target) || bad_chans(in_chans))
+        (loss_partials && !target) || bad_chans(in_chans) || bad_r(r))
         return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
@@ -1016,6 +1375,17 @@ extern "C" int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const flo
     const TailNorm nrm{x, gamma, beta, eps, (bf16_t*)xn, mean, rstd};
     const TailLoss ls{target, loss_partials, log_transform};
     const int ks = (E + 31) / 32;
+    if (r == 8) {
+        const bf16_t* none = nullptr;
+#define TULIP_TFL8(NCH) \
+    if (ks <= 2) hipLaunchKernelGGL((tail8_fwd_kernel<2, NCH, true>), grid, block, 0, stream, nrm, none, (const bf16_t*)We, be, wd, pred, g, ls); \
+    else if (ks == 3) hipLaunchKernelGGL((tail8_fwd_kernel<3, NCH, true>), grid, block, 0, stream, nrm, none, (const bf16_t*)We, be, wd, pred, g, ls); \
+    else hipLaunchKernelGGL((tail8_fwd_kernel<4, NCH, true>), grid, block, 0, stream, nrm, none, (const bf16_t*)We, be, wd, pred, g, ls);
+        TULIP_NCH_SWITCH(TULIP_TFL8)
+#undef TULIP_TFL8
+        TULIP_CHECK_LAUNCH();
+        return TULIP_OK;
+    }
 #define TULIP_TFL(NCH) \
     if (ks <= 2) hipLaunchKernelGGL((tail_fwd_ln_kernel<2, NCH>), grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls); \
     else if (ks == 3) hipLaunchKernelGGL((tail_fwd_ln_kernel<3, NCH>), grid, block, 0, stream, nrm, (const bf16_t*)We, be, wd, pred, g, ls); \
@@ -1026,19 +1396,32 @@ extern "C" int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const flo
     return TULIP_OK;
 }
 
+extern "C" int tulip_tail_fwd_ln_c(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
+                                   float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
+                                   const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
+                                   hipStream_t stream, int in_chans) {
+    return tulip_tail_fwd_ln_r(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, target, loss_partials, log_transform, B, H, W,
+                               E, stream, in_chans, 4);
+}
+
 extern "C" int tulip_tail_fwd_ln(const float* x, const float* gamma, const float* beta, float eps, uint16_t* xn, float* mean,
                                  float* rstd, const uint16_t* We, const float* be, const float* wd, float* pred,
                                  const float* target, float* loss_partials, int log_transform, int B, int H, int W, int E,
                                  hipStream_t stream) {
-    return tulip_tail_fwd_ln_c(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, target, loss_partials, log_transform, B, H, W,
-                               E, stream, 1);
+    return tulip_tail_fwd_ln_r(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, target, loss_partials, log_transform, B, H, W,
+                               E, stream, 1, 4);
 }
 
 // channels per workgroup of tulip_tail_wgrad: 8 waves x 3 (E % 24 == 0; 256 registers per wave) or 4 waves x 4; about one
-// workgroup per CU
-static void tail_wgrad_plan(int M, int E, int* nslices, int* splits, int* steps_per_split) {
+// workgroup per CU.  r = 8: the 4E virtual channels, 8 waves x wgrad8_nc (the widest slice whose accumulators, with the
+// in_chans pred / target planes in flight, stay in registers: 3 at in_chans 1 and E = 48 / 96, else 2; 1 at E = 128 x 4 planes)
+static constexpr int wgrad8_nc(int E, int in_chans) {
+    return (E % 48 == 0 && in_chans == 1) ? 3 : (E == 128 && in_chans == 4) ? 1 : 2;
+}
+static void tail_wgrad_plan(int M, int E, int r, int in_chans, int* nslices, int* splits, int* steps_per_split) {
     const int total = (M + 31) / 32;
-    *nslices = E / ((E % 24 == 0) ? 24 : 16);
+    if (r == 8) *nslices = 4 * E / (8 * wgrad8_nc(E, in_chans));
+    else *nslices = E / ((E % 24 == 0) ? 24 : 16);
     int sp = 256 / *nslices;
     if (sp < 1) sp = 1;
     if (sp > total) sp = total;
@@ -1046,30 +1429,34 @@ static void tail_wgrad_plan(int M, int E, int* nslices, int* splits, int* steps_
     *splits = (total + *steps_per_split - 1) / *steps_per_split;
 }
 
-extern "C" int tulip_tail_wgrad_splits(int B, int H, int W, int E) {
-    if (!tulip_tail_fused_bwd_supported(E) || B * H * W <= 0) return 0;
+extern "C" int tulip_tail_wgrad_splits_r(int B, int H, int W, int E, int in_chans, int r) {
+    if (!tulip_tail_fused_bwd_supported_r(E, r) || B * H * W <= 0 || bad_chans(in_chans)) return 0;
     int ns, sp, st;
-    tail_wgrad_plan(B * H * W, E, &ns, &sp, &st);
+    tail_wgrad_plan(B * H * W, E, r, in_chans, &ns, &sp, &st);
     return sp;
 }
 
-extern "C" int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+extern "C" int tulip_tail_wgrad_splits(int B, int H, int W, int E) { return tulip_tail_wgrad_splits_r(B, H, W, E, 1, 4); }
+
+extern "C" int tulip_tail_wgrad_r(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                                   float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
-                                  const float* gscale_dev, float gscale, hipStream_t stream, int in_chans) {
-    if (!tulip_tail_fused_bwd_supported(E) || !xn || !We || !be || !wd || !dpred || !slabs_w || !slabs_b || bad_chans(in_chans))
+                                  const float* gscale_dev, float gscale, hipStream_t stream, int in_chans, int r) {
+    if (!tulip_tail_fused_bwd_supported_r(E, r) || !xn || !We || !be || !wd || !dpred || !slabs_w || !slabs_b || bad_chans(in_chans))
         return TULIP_ERR_ARG;
     TailGeom g{B * H * W, H, W, E};
     if (g.M <= 0) return TULIP_OK;
     int ns, sp, st;
-    tail_wgrad_plan(g.M, E, &ns, &sp, &st);
+    tail_wgrad_plan(g.M, E, r, in_chans, &ns, &sp, &st);
     const bool wide = E % 24 == 0;
-    const dim3 grid(ns * sp), block(wide ? 512 : 256);
+    const dim3 grid(ns * sp), block(wide || r == 8 ? 512 : 256);
     const int wsh = (W >= 32 && (W & (W - 1)) == 0) ? 31 - __builtin_clz((unsigned)W) : -1;
+#define TULIP_TWG_K(KS, NB, NC, NWV, NCH, UP) \
+    hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, NC, NWV, NCH, UP>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
+                       target, gscale_dev, gscale, slabs_w, slabs_b, g, ns, st, wsh)
 #define TULIP_TWG(KS, NB, NCH) \
-    do { if (wide) hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 3, 8, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
-                       target, gscale_dev, gscale, slabs_w, slabs_b, g, ns, st, wsh); \
-         else hipLaunchKernelGGL((tail_wgrad_kernel<KS, NB, 4, 4, NCH>), grid, block, 0, stream, (const bf16_t*)xn, (const bf16_t*)We, be, wd, dpred, \
-                       target, gscale_dev, gscale, slabs_w, slabs_b, g, ns, st, wsh); } while (0)
+    do { if (r == 8) TULIP_TWG_K(KS, NB, wgrad8_nc(16 * NB, NCH), 8, NCH, 8); \
+         else if (wide) TULIP_TWG_K(KS, NB, 3, 8, NCH, 4); \
+         else TULIP_TWG_K(KS, NB, 4, 4, NCH, 4); } while (0)
 #define TULIP_TWG_E(NCH) \
     switch (E / 16) { \
         case 1: TULIP_TWG(1, 1, NCH); break; \
@@ -1084,12 +1471,19 @@ extern "C" int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const 
     TULIP_NCH_SWITCH(TULIP_TWG_E)
 #undef TULIP_TWG_E
 #undef TULIP_TWG
+#undef TULIP_TWG_K
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
+}
+
+extern "C" int tulip_tail_wgrad_c(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
+                                  float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
+                                  const float* gscale_dev, float gscale, hipStream_t stream, int in_chans) {
+    return tulip_tail_wgrad_r(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target, gscale_dev, gscale, stream, in_chans, 4);
 }
 
 extern "C" int tulip_tail_wgrad(const uint16_t* xn, const uint16_t* We, const float* be, const float* wd, const float* dpred,
                                 float* slabs_w, float* slabs_b, int B, int H, int W, int E, const float* target,
                                 const float* gscale_dev, float gscale, hipStream_t stream) {
-    return tulip_tail_wgrad_c(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target, gscale_dev, gscale, stream, 1);
+    return tulip_tail_wgrad_r(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target, gscale_dev, gscale, stream, 1, 4);
 }

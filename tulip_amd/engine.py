@@ -279,7 +279,8 @@ class Plan:
         H0, W0 = eng.grid
         self.f32 = lambda name, *shape: self._alloc(name, shape, torch.float32, dev)
         self.b16 = lambda name, *shape: self._alloc(name, shape, torch.bfloat16, dev)
-        Hh, Wh = m.target_img_size
+        r = m.upscale_factor
+        Hh, Wh = H0 * r, W0 * r                    # the output image is grid * r (tulip.py:727-731), whatever target_img_size says
         self.x_in = self.f32("x_in", B, m.in_chans, m.img_size[0], m.img_size[1])
         self.target = self.f32("target", B, m.in_chans, Hh, Wh)
         self.pred = self.f32("pred", B, m.in_chans, Hh, Wh)
@@ -343,9 +344,9 @@ class Plan:
         big = max(4 * (B * (H0 >> s) * (W0 >> s) // 4) * (E << s) for s in range(nl))
         self.b16("t.dxm", big)                     # dgrad of a merge reduction [M/4][4C]
         self.b16("tail.xn", maxM, E); self.f32("tail.mean", maxM); self.f32("tail.rstd", maxM)
-        self.b16("tail.dz", maxM, 16 * E)
+        r2 = r * r
+        self.b16("tail.dz", maxM, r2 * E)
         if not m.pixel_shuffle:                    # FinalPatchExpanding (tulip.py:144-159)
-            r2 = m.upscale_factor ** 2
             self.f32("tail.ey", maxM, r2 * E); self.f32("tail.emean", r2 * maxM); self.f32("tail.erstd", r2 * maxM)
         self.b16("tail.dxn", maxM, E)
         # partial-row workspaces of the atomic-free reductions
@@ -402,16 +403,23 @@ class TulipEngine:
         if not 1 <= m.in_chans <= 4:
             raise NotImplementedError(f"tulip_amd supports in_chans 1 to 4 (got {m.in_chans}): the patch embedding and the "
                                       f"fused head are instantiated for at most 4 image channels")
-        if m.in_chans > 1:
-            kw = 8 if m.circular_padding else m.patch_size[1]
-            taps = m.in_chans * m.patch_size[0] * kw
-            if taps > 16 and m.embed_dim not in (48, 96):
-                raise NotImplementedError(f"tulip_amd patch-embedding backward covers {taps} taps (in_chans * patch height * "
-                                          f"kernel width) only at embed_dim 48 or 96 (got {m.embed_dim})")
-            if not m.pixel_shuffle and m.embed_dim > 256:
-                raise NotImplementedError("tulip_amd FinalPatchExpanding with in_chans > 1 supports embed_dim <= 256")
-        if m.upscale_factor != 4:
-            raise NotImplementedError("tulip_amd fused head supports upscale_factor == 4 (every BASELINE config)")
+        if m.upscale_factor not in (4, 8):
+            raise NotImplementedError(
+                f"tulip_amd heads support upscale_factor 4 and 8 (got {m.upscale_factor}): the factor is int(sqrt(target area / image "
+                f"area)) * 2 * int(sqrt(patch area // 4)) (tulip.py:577), i.e. 4 for patches of 4 to 15 pixels and 8 for 16-pixel "
+                f"patches such as (2, 8) and (4, 4) at a 4x larger target; 2 ((2, 2) patches on equal sizes) and 16 (64-pixel "
+                f"patches) are not built")
+        # patch-embedding taps = in_chans * patch height * kernel width (8 with circular padding): up to 16 at any embed_dim, up to
+        # 32 at embed_dim 48 / 96 (the backward's 16-lane form), e.g. (4, 4) patches with circular padding or in_chans 2 at (2, 8)
+        kw = 8 if m.circular_padding else m.patch_size[1]
+        taps = m.in_chans * m.patch_size[0] * kw
+        if taps > 32 or (taps > 16 and m.embed_dim not in (48, 96)):
+            raise NotImplementedError(f"tulip_amd patch embedding covers at most 16 taps (in_chans * patch height * kernel width), "
+                                      f"32 taps at embed_dim 48 or 96; got {taps} taps at embed_dim {m.embed_dim}")
+        if m.circular_padding and m.patch_size[1] not in (4, 8):
+            raise NotImplementedError(f"tulip_amd circular padding supports patch widths 4 and 8 (got patch_size {m.patch_size})")
+        if m.in_chans > 1 and not m.pixel_shuffle and m.embed_dim > 256:
+            raise NotImplementedError("tulip_amd FinalPatchExpanding with in_chans > 1 supports embed_dim <= 256")
         ws = m.window_size if isinstance(m.window_size, (tuple, list)) else (m.window_size, m.window_size)
         self.window = (int(ws[0]), int(ws[1]))
         # tokens per window: the attention kernels cover L = 16 (fused block kernels, fp8 scores) and L = 32 / 64
@@ -1154,7 +1162,7 @@ class TulipEngine:
                             P["tail.rstd"], W_.p16("ps_head.conv_expand.0.weight"), W_.p32("ps_head.conv_expand.0.bias"),
                             W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, target=P.target if with_loss else None,
                             loss_partials=P.partials if with_loss else None, log_transform=m.log_transform,
-                            in_chans=m.in_chans)
+                            in_chans=m.in_chans, r=m.upscale_factor)
             if with_loss:
                 fin = lambda: ops.l1_loss_final(P.partials, P.losses, (M0 + 31) // 32, P.pred.numel(), m.log_transform)
                 if defer_loss_final:
@@ -1166,7 +1174,7 @@ class TulipEngine:
             ops.layernorm_fwd(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), P["tail.xn"], P["tail.mean"],
                               P["tail.rstd"], M0, E, self.eps)
             ops.tail_fwd(P["tail.xn"], W_.p16("ps_head.conv_expand.0.weight"), W_.p32("ps_head.conv_expand.0.bias"),
-                         W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, in_chans=m.in_chans)
+                         W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, in_chans=m.in_chans, r=m.upscale_factor)
         else:
             # FinalPatchExpanding (tulip.py:144-159) + decoder_pred (tulip.py:731): Linear E -> r^2 E, then one kernel
             # for rearrange + LayerNorm(E) + the 1x1 conv as a per-row dot product
@@ -1876,9 +1884,11 @@ class TulipEngine:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
             targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred)
+            r = m.upscale_factor
+            NE = r * r * E                              # output channels of the expand conv
             tkw = dict(target=P.target, gscale_dev=gscale_dev, gscale=gscale,   # L1 backward (tulip.py:692-693) formed in-kernel
-                       in_chans=m.in_chans)
-            self._tail_fused = self.fuse_tail_bwd and ops.tail_fused_bwd_supported(E)
+                       in_chans=m.in_chans, r=r)
+            self._tail_fused = self.fuse_tail_bwd and ops.tail_fused_bwd_supported(E, r)
             if self._tail_fused:
                 # d(expand pre-activation) -- 100 MB at batch 8 -- is never written: the chain's kernel goes straight to dxn,
                 # the side queue's kernel recomputes it channel-sliced for the expand conv's weight / bias gradient
@@ -1897,15 +1907,15 @@ class TulipEngine:
                     self._fold(lnp + 4 * E, 2 * E, G("norm_up.bias"), E, R)
                 else:
                     ops.tail_bwd_dgrad(*targs, P["tail.dxn"], tpart, B, H0, W0, E, **tkw)
-                sp = ops.tail_wgrad_splits(B, H0, W0, E)
-                nw = 16 * E * E
-                slab = P.scratch("tail.wslab", sp * (nw + 16 * E))
+                sp = ops.tail_wgrad_splits(B, H0, W0, E, m.in_chans, r)
+                nw = NE * E
+                slab = P.scratch("tail.wslab", sp * (nw + NE))
                 self._side_first(lambda: ops.tail_wgrad(*targs, slab, slab + 4 * sp * nw, B, H0, W0, E, **tkw))
                 self._fold(slab, nw, G(head_w), nw, sp)
-                self._fold(slab + 4 * sp * nw, 16 * E, G(head_b), 16 * E, sp)
+                self._fold(slab + 4 * sp * nw, NE, G(head_b), NE, sp)
             else:
                 ops.tail_bwd(*targs, P["tail.dz"], tpart, B, H0, W0, E, **tkw)
-                self._wgrad(P["tail.dz"], 16 * E, P["tail.xn"], E, 16 * E, E, M0, G(head_w), G(head_b))
+                self._wgrad(P["tail.dz"], NE, P["tail.xn"], E, NE, E, M0, G(head_w), G(head_b))
             if m.in_chans == 1:
                 self._fold(tpart, 128, gdw, E, (M0 + 31) // 32)
             else:
@@ -1916,6 +1926,7 @@ class TulipEngine:
             # FinalPatchExpanding backward: d(pred) (L1, tulip.py:692-693) -> decoder_pred / LayerNorm backward per fine
             # token -> tail.dz = d(Linear output) in the Linear's layout
             r = m.upscale_factor
+            NE = r * r * E
             pre = "final_patch_expanding"
             ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
             R = ops.expand_norm_bwd_partial_rows(B, H0, W0, r)
@@ -1928,9 +1939,9 @@ class TulipEngine:
             self._fold(part + 4 * E, nrow, G(pre + ".norm.bias"), E, R)
             self._fold(part + 8 * E, nrow, gdw, m.in_chans * E, R)
             head_w = pre + ".expand.weight"
-            self._wgrad(P["tail.dz"], 16 * E, P["tail.xn"], E, 16 * E, E, M0, G(head_w))
+            self._wgrad(P["tail.dz"], NE, P["tail.xn"], E, NE, E, M0, G(head_w))
         if not (m.pixel_shuffle and self._tail_fused):
-            self._gemm(P["tail.dz"], W_.p16(head_w), M0, E, 16 * E, lda=16 * E, ldb=E, b_trans=True,
+            self._gemm(P["tail.dz"], W_.p16(head_w), M0, E, NE, lda=NE, ldb=E, b_trans=True,
                      epi=EPI_BF16, out=P["tail.dxn"], ldo=E)
         x_last = P[self.dec_blocks[-1][-1].prefix + ".out"] if nl > 1 else P[self.enc_blocks[0][-1].prefix + ".out"]
         dx = P["dec0.dx"] if nl > 1 else P["enc0.dx"]
@@ -2164,6 +2175,20 @@ class TulipEngine:
                               lambda: self.run_backward(P, g, gscale_dev=P._mod_gscale, gscale=1.0, overwrite=over))
         return g.clone() if which == 2 else g
 
+    def output_shape(self, B: int):
+        """(B, in_chans, grid_h * r, grid_w * r): pred and the target (tulip.py:727-731) -- not target_img_size for every model"""
+        r = self.model.upscale_factor
+        return (B, self.model.in_chans, self.grid[0] * r, self.grid[1] * r)
+
+    def check_target(self, B: int, target):
+        """upscale_factor 8: the target must be exactly the output image -- for TULIP() with the constructor defaults that is
+        64x4096 against target_img_size (128, 2048), and a reshape would silently scramble such a target.  Raised before any
+        launch.  The 4x models keep their permissive reshape."""
+        want = self.output_shape(B)
+        if self.model.upscale_factor != 4 and tuple(target.shape) != want:
+            raise ValueError(f"target shape {tuple(target.shape)} is not the model's output shape {want} "
+                             f"(batch, in_chans, token grid {self.grid} * upscale_factor {self.model.upscale_factor})")
+
     def autograd_forward(self, x, target, mc_drop: bool):
         self.bind(x.device)
         self.params.shadow_dirty = True  # parameters may have been updated by a foreign optimizer
@@ -2175,6 +2200,7 @@ class TulipEngine:
             self.run_forward(P, with_loss=False)
             self.params.shadow_dirty = True
             return P.pred.clone()
+        self.check_target(B, target)
         P.target.copy_(target.reshape(P.target.shape).float())
         params = self._cur_params if self._cur_params is not None else self.params.current_params(self.model)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)

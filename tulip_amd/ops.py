@@ -234,42 +234,44 @@ def cast_bf16_f32(x, y, n):
     check(_lib.load().tulip_cast_bf16_f32(_p(x), _p(y), n, _stream()), "tulip_cast_bf16_f32")
 
 
-def tail_fwd(xn, We, be, wd, pred, B, H, W, E, in_chans=1):
-    check(_lib.load().tulip_tail_fwd_c(_p(xn), _p(We), _p(be), _p(wd), _p(pred), B, H, W, E, _stream(), int(in_chans)),
-          "tulip_tail_fwd_c")
+def tail_fwd(xn, We, be, wd, pred, B, H, W, E, in_chans=1, r=4):
+    """r: the head's upscale factor (4 or 8; pred is (B, in_chans, r H, r W), We [r*r*E][E]) -- of every tail_* call below"""
+    check(_lib.load().tulip_tail_fwd_r(_p(xn), _p(We), _p(be), _p(wd), _p(pred), B, H, W, E, _stream(), int(in_chans), int(r)),
+          "tulip_tail_fwd_r")
 
 
-def tail_bwd(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
-    check(_lib.load().tulip_tail_bwd_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dz), _p(dwd), B, H, W, E,
-                                       _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)), "tulip_tail_bwd_c")
+def tail_bwd(xn, We, be, wd, dpred, dz, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1, r=4):
+    check(_lib.load().tulip_tail_bwd_r(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dz), _p(dwd), B, H, W, E,
+                                       _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans), int(r)),
+          "tulip_tail_bwd_r")
 
 
-def tail_fused_bwd_supported(E):
-    return bool(_lib.load().tulip_tail_fused_bwd_supported(int(E)))
+def tail_fused_bwd_supported(E, r=4):
+    return bool(_lib.load().tulip_tail_fused_bwd_supported_r(int(E), int(r)))
 
 
-def tail_bwd_dgrad(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
+def tail_bwd_dgrad(xn, We, be, wd, dpred, dxn, dwd, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1, r=4):
     """Head backward on the chain: dxn (bf16 [M][E]) and the decoder_pred partial rows; d(expand) is never written."""
-    check(_lib.load().tulip_tail_bwd_dgrad_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dxn), _p(dwd), B, H, W, E,
-                                             _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)),
-          "tulip_tail_bwd_dgrad_c")
+    check(_lib.load().tulip_tail_bwd_dgrad_r(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dxn), _p(dwd), B, H, W, E,
+                                             _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans), int(r)),
+          "tulip_tail_bwd_dgrad_r")
 
 
 def tail_bwd_dgrad_ln(xn, We, be, wd, dpred, dwd, B, H, W, E, x, mean, rstd, gamma, dx, ln_partials, dx_bf16=None,
-                      cast_rowscale=None, cast_rows_per_sample=1, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
+                      cast_rowscale=None, cast_rows_per_sample=1, target=None, gscale_dev=None, gscale=1.0, in_chans=1, r=4):
     """tail_bwd_dgrad with norm_up's backward in the epilogue: dx / dx_bf16 / [dgamma | dbeta] partial rows (one per 32 tokens)."""
-    check(_lib.load().tulip_tail_bwd_dgrad_ln_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dwd), B, H, W, E, _p(target),
+    check(_lib.load().tulip_tail_bwd_dgrad_ln_r(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(dwd), B, H, W, E, _p(target),
                                                 _p(gscale_dev), float(gscale), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx),
                                                 _p(dx_bf16), _p(cast_rowscale), cast_rows_per_sample, _p(ln_partials),
-                                                _stream(), int(in_chans)), "tulip_tail_bwd_dgrad_ln_c")
+                                                _stream(), int(in_chans), int(r)), "tulip_tail_bwd_dgrad_ln_r")
 
 
 def tail_fwd_ln(x, gamma, beta, eps, xn, mean, rstd, We, be, wd, pred, B, H, W, E, target=None, loss_partials=None,
-                log_transform=False, in_chans=1):
+                log_transform=False, in_chans=1, r=4):
     """norm_up + fused head (+ the L1 / pixel loss partial sums per 32 tokens) in one launch."""
-    check(_lib.load().tulip_tail_fwd_ln_c(_p(x), _p(gamma), _p(beta), float(eps), _p(xn), _p(mean), _p(rstd), _p(We), _p(be),
+    check(_lib.load().tulip_tail_fwd_ln_r(_p(x), _p(gamma), _p(beta), float(eps), _p(xn), _p(mean), _p(rstd), _p(We), _p(be),
                                           _p(wd), _p(pred), _p(target), _p(loss_partials), int(log_transform), B, H, W, E,
-                                          _stream(), int(in_chans)), "tulip_tail_fwd_ln_c")
+                                          _stream(), int(in_chans), int(r)), "tulip_tail_fwd_ln_r")
 
 
 def l1_loss_final(partials, losses, nblocks, n, log_transform):
@@ -277,15 +279,15 @@ def l1_loss_final(partials, losses, nblocks, n, log_transform):
           "tulip_l1_loss_final")
 
 
-def tail_wgrad_splits(B, H, W, E):
-    return _lib.load().tulip_tail_wgrad_splits(B, H, W, E)
+def tail_wgrad_splits(B, H, W, E, in_chans=1, r=4):
+    return _lib.load().tulip_tail_wgrad_splits_r(B, H, W, E, int(in_chans), int(r))
 
 
-def tail_wgrad(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1):
+def tail_wgrad(xn, We, be, wd, dpred, slabs_w, slabs_b, B, H, W, E, target=None, gscale_dev=None, gscale=1.0, in_chans=1, r=4):
     """Expand-conv weight / bias gradient of the head as token-split slabs, d(expand) recomputed channel-sliced."""
-    check(_lib.load().tulip_tail_wgrad_c(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(slabs_w), _p(slabs_b), B, H, W, E,
-                                         _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans)),
-          "tulip_tail_wgrad_c")
+    check(_lib.load().tulip_tail_wgrad_r(_p(xn), _p(We), _p(be), _p(wd), _p(dpred), _p(slabs_w), _p(slabs_b), B, H, W, E,
+                                         _p(target), _p(gscale_dev), float(gscale), _stream(), int(in_chans), int(r)),
+          "tulip_tail_wgrad_r")
 
 
 def expand_norm_fwd(y, gamma, beta, mean, rstd, B, H, W, P, Cn, eps, out_bf16=None, ld=0, dotw=None, pred=None, in_chans=1):

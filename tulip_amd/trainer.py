@@ -584,6 +584,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ public
     def load_batch(self, x: torch.Tensor, target: torch.Tensor):
+        self.eng.check_target(self.P.B, target)
         self.P.x_in.copy_(x.reshape(self.P.x_in.shape), non_blocking=True)
         self.P.target.copy_(target.reshape(self.P.target.shape), non_blocking=True)
 

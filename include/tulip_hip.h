@@ -141,6 +141,22 @@ int tulip_wgrad_group_adamw(const tulip_wgrad_item* items, int n, const tulip_re
  * tulip_wgrad_group_adamw marks the fold regions of its token-split items with reserved_ = 1 this way (weight and bias).
  * adam == NULL: exactly tulip_reduce_rows_multi (a marked region is then an argument error). */
 int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions, int n, const tulip_adamw_ref* adam, hipStream_t stream);
+/* Per-group learning-rate scales (layer-wise lr decay: timm's `lr_scale`, applied by the reference's schedule as
+ * lr * lr_scale, util/lr_sched.py:16-20).  The `_s` twins of the four entry points that take the AdamW step read the group of
+ * every 64-float block from bits 2-7 of its decay_mask64 byte (bit 0: decay, bit 1: stepped elsewhere) and step it with
+ * lr_g = fl32(hyper[0] * lr_scale64[group]) in place of hyper[0], in 1 - lr wd and in lr / bias_corr1 alike.  lr_scale64: a
+ * device table of 64 floats whose entry 0 is 1.0f (blocks with bits 2-7 clear keep hyper[0]: x * 1.0f is exact).
+ * lr_scale64 == NULL: exactly the entry point without the suffix, which never reads bits 2-7.  lr_scale64 without a mask
+ * (decay_mask64 / adam->decay_mask64 NULL, or adam NULL) is TULIP_ERR_ARG before any launch.  A weight-gradient write-out steps
+ * one tensor per item and takes the group from the mask byte of the tensor's first block, decay_mask64[(dW - adam->grad) / 64].
+ * REQUIREMENT with a table: every stepped item's dW starts on a 64-float boundary of adam->grad and no 64-float block holds
+ * elements of two groups (the host cannot check the latter: a tensor that starts inside a block is stepped at the rate of the
+ * tensor the block begins with).  An item whose dW is not 64-float aligned to adam->grad is TULIP_ERR_ARG before any launch. */
+int tulip_wgrad_group_adamw_s(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
+                              void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam,
+                              const float* lr_scale64, hipStream_t stream);
+int tulip_reduce_rows_multi_adamw_s(const tulip_reduce_region* regions, int n, const tulip_adamw_ref* adam,
+                                    const float* lr_scale64, hipStream_t stream);
 /* The fold regions tulip_wgrad_group(fold = 1) would hand to tulip_reduce_rows_multi for these items and this workspace (host
  * code only): for a caller that launches with fold = 0 and folds later, in one launch with regions that become ready in
  * between (the engine: the patch-embedding partial rows ride in the fold of the backward's last weight-gradient group).
@@ -430,6 +446,14 @@ int tulip_adamw(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_
  * (tulip_wgrad_group_adamw, tulip_reduce_rows_multi_adamw) -- nothing is scanned. */
 int tulip_adamw_blocks(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
                        const float* hyper, const uint8_t* decay_mask64, int zero_grad, hipStream_t stream);
+/* tulip_adamw / tulip_adamw_blocks with per-group learning-rate scales (see tulip_wgrad_group_adamw_s): block i/64 is stepped
+ * with lr_g = fl32(hyper[0] * lr_scale64[decay_mask64[i/64] >> 2]); bits 0 and 1 of the mask byte keep their meaning.
+ * lr_scale64 == NULL: exactly tulip_adamw / tulip_adamw_blocks; lr_scale64 with decay_mask64 == NULL: TULIP_ERR_ARG. */
+int tulip_adamw_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, const float* hyper,
+                  const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad, hipStream_t stream);
+int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
+                         const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
+                         hipStream_t stream);
 
 /* DropPath multipliers of one step (tulip.py:25-29; timm drop_path: keep a sample's residual branch with
  * probability keep, scale kept branches by 1/keep): scale[slot*B+b] = floor(keep[slot] + u)/keep[slot] with

@@ -82,6 +82,7 @@ class SkipUnmergeBwdDesc(ctypes.Structure):    # tulip_skip_unmerge_bwd_desc
 
 
 REDUCE_REGIONS_MAX, WGRAD_GROUP_MAX, PACK_MAX = 48, 16, 64
+LR_GROUP_SHIFT, LR_GROUPS_MAX = 2, 64      # decay_mask64 bits 2-7: the block's learning-rate group (TULIP_LR_GROUP_SHIFT, csrc/common.h)
 GEMM_NO_TOUCH, GEMM_CHECKED, GEMM_NO_MID, GEMM_MID, WGRAD_SMALL_TILES, BLOCK_NO_WARM = 0x100, 0x200, 0x400, 0x800, 0x100, 8     # per-call flag bits (tulip_hip.h)
 GEMM_B_PACKED = 0x1000
 ABI_VERSION = 6      # TULIP_ABI_VERSION of include/tulip_hip.h: the ctypes structs above mirror that layout
@@ -171,6 +172,11 @@ SIGNATURES = {
     "tulip_l1_loss_bwd": [P, P, P, F, P, L, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
+    # ... and with a trailing-but-one lr_scale64 table: per-group learning-rate scales (group = mask byte >> 2)
+    "tulip_adamw_s": [P, P, P, P, P, L, P, P, P, I, P],
+    "tulip_adamw_blocks_s": [P, P, P, P, P, P, I, P, P, P, I, P],
+    "tulip_wgrad_group_adamw_s": [P, I, P, I, P, L, I, P, P, P],
+    "tulip_reduce_rows_multi_adamw_s": [P, I, P, P, P],
     "tulip_drop_path_scales": [P, P, P, I, I, ctypes.c_uint64, P, P],
     "tulip_dropout_begin": [P, P, I, P],
     "tulip_dropout_mask": [P, ctypes.c_uint64, I, F, L, P, P],

@@ -61,6 +61,15 @@ __device__ __forceinline__ AdamwCoef adamw_coef(const float* __restrict__ hyper,
     const float lr = hyper[0], wd = hyper[4];
     return AdamwCoef{hyper[1], hyper[2], hyper[3], decay_on ? 1.0f - lr * wd : 1.0f, lr / hyper[5], rsqrtf(hyper[6]), hyper[7]};
 }
+// The same coefficients at a group's own learning rate (layer-wise lr decay, timm's `lr_scale`): lr_g = fl32(lr * lr_scale) takes the
+// place of lr in both terms that hold it, 1 - lr wd and lr / bias_corr1.  The group of a 64-float block is bits 2-7 of its
+// decay_mask64 byte (bit 0: decay, bit 1: stepped elsewhere), lr_scale = table[group] from a 64-float device table whose entry 0
+// is 1.0f -- the kernels instantiated without a table never form the product, so their code is the one without this overload.
+#define TULIP_LR_GROUP_SHIFT 2
+__device__ __forceinline__ AdamwCoef adamw_coef(const float* __restrict__ hyper, bool decay_on, float lr_scale) {
+    const float lr = hyper[0] * lr_scale, wd = hyper[4];
+    return AdamwCoef{hyper[1], hyper[2], hyper[3], decay_on ? 1.0f - lr * wd : 1.0f, lr / hyper[5], rsqrtf(hyper[6]), hyper[7]};
+}
 __device__ __forceinline__ void adamw_step4(float4& pp, float4& mm, float4& vv, const float4 gg, const AdamwCoef c) {
 #pragma clang fp contract(off)
     float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; const float* G = (const float*)&gg;
@@ -131,7 +140,8 @@ __device__ __forceinline__ float4 fold_slabs4(const float* __restrict__ p, size_
 
 // The flat optimizer buffers of a step taken outside adamw_kernel (tulip_adamw_ref): an element is addressed by the offset of its
 // gradient from g0; mask64 (optional): one byte per 64 elements, bit 0 = decoupled weight decay applies (NULL: everywhere).
-struct AdamRef { const float* hyper; const float* g0; float* p0; float* m0; float* v0; bf16_t* pb0; const uint8_t* mask64; };
+// lr_scale (optional, needs mask64): the 64-float table of per-group learning-rate scales, indexed by bits 2-7 of the block's mask byte.
+struct AdamRef { const float* hyper; const float* g0; float* p0; float* m0; float* v0; bf16_t* pb0; const uint8_t* mask64; const float* lr_scale; };
 
 // A bf16 MFMA operand that was JUST packed by vector-ALU instructions (v_cvt_pk_bf16_f32 behind an fma): pin 8 wait states
 // between the pack and the MFMAs that read it.  Measured on gfx950 / ROCm 7.2 (tools/det_tail_instep.py): without them the

@@ -102,6 +102,8 @@ struct MultiRegion {
 // producer of these tensors in this backward), so the AdamW step (adamw_step4, common.h: the arithmetic of adamw_kernel) is
 // taken right here and the gradient is never stored; the end-of-step AdamW skips the tensors (mask bit 1)
 struct MultiRegions { MultiRegion r[TULIP_REDUCE_REGIONS_MAX]; int n; AdamRef ad; };
+// SC: the stepped regions take each block's learning-rate scale from ad.lr_scale (adamw_coef, common.h); false: the code without it
+template <bool SC>
 __global__ __launch_bounds__(256) void reduce_rows_multi_kernel(const MultiRegions R) {
     __shared__ float4 red[256];
     int i = 0;
@@ -186,8 +188,13 @@ __global__ __launch_bounds__(256) void reduce_rows_multi_kernel(const MultiRegio
             if (r.adam) {                               // block-uniform
                 const AdamRef& ad = R.ad;
                 const size_t idx = aidx;
-                const bool decay = ad.mask64 ? (ad.mask64[idx >> 6] & 1u) != 0 : true;
-                adamw_step4(pp, mm, vv, o, adamw_coef(ad.hyper, decay));
+                if constexpr (SC) {
+                    const unsigned mk = ad.mask64[idx >> 6];
+                    adamw_step4(pp, mm, vv, o, adamw_coef(ad.hyper, (mk & 1u) != 0, ad.lr_scale[mk >> TULIP_LR_GROUP_SHIFT]));
+                } else {
+                    const bool decay = ad.mask64 ? (ad.mask64[idx >> 6] & 1u) != 0 : true;
+                    adamw_step4(pp, mm, vv, o, adamw_coef(ad.hyper, decay));
+                }
                 st_state(ad.p0 + idx, pp); st_state(ad.m0 + idx, mm); st_state(ad.v0 + idx, vv);
                 st_state_bf16x4(ad.pb0 + idx, make_uint2(pack_bf16x2(pp.x, pp.y), pack_bf16x2(pp.z, pp.w)));
             } else {
@@ -244,11 +251,20 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ p
 
 // ---------------------------------------------------------------- AdamW
 // hyper = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}
+// SC: lr_scale[mask byte >> 2] scales the learning rate of the block (adamw_coef, common.h; mask64 is then required) and the
+// coefficients are formed per block; otherwise the two launch-uniform sets (decay / no decay) are formed once at entry
+template <bool SC>
+__device__ __forceinline__ AdamwCoef adamw_coef_uniform(const float* __restrict__ hyper, bool decay_on) {
+    if constexpr (SC) return AdamwCoef{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (never read: every block has its own)
+    else return adamw_coef(hyper, decay_on);
+}
+template <bool SC>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ pb, int64_t n, const float* __restrict__ hyper,
-                                                    const uint8_t* __restrict__ mask64, int zero_grad) {
-    const AdamwCoef cd = adamw_coef(hyper, true), cn = adamw_coef(hyper, false);
+                                                    const uint8_t* __restrict__ mask64, const float* __restrict__ lr_scale,
+                                                    int zero_grad) {
+    [[maybe_unused]] const AdamwCoef cd = adamw_coef_uniform<SC>(hyper, true), cn = adamw_coef_uniform<SC>(hyper, false);
     const int64_t n4 = n >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const unsigned mk = mask64 ? mask64[i >> 4] : 1u;
@@ -256,7 +272,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
         float4 pp = *(float4*)(p + i * 4);
         const float4 gg = *(const float4*)(g + i * 4);
         float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
-        adamw_step4(pp, mm, vv, gg, (mk & 1u) ? cd : cn);
+        if constexpr (SC) adamw_step4(pp, mm, vv, gg, adamw_coef(hyper, (mk & 1u) != 0, lr_scale[mk >> TULIP_LR_GROUP_SHIFT]));
+        else adamw_step4(pp, mm, vv, gg, (mk & 1u) ? cd : cn);
         *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
         if (zero_grad) *(float4*)(g + i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
         if (pb) *(uint2*)(pb + i * 4) = make_uint2(pack_bf16x2(pp.x, pp.y), pack_bf16x2(pp.z, pp.w));
@@ -265,12 +282,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 
 // the same step over an explicit list of 64-element blocks (the few tensors left for the end of the step once everything else was
 // stepped where its gradient was completed): 16 lanes per block, nothing scanned
+template <bool SC>
 __global__ __launch_bounds__(256) void adamw_kernel_blocks(float* __restrict__ p, float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v,
                                                            bf16_t* __restrict__ pb, const int32_t* __restrict__ blocks,
                                                            int nblocks, const float* __restrict__ hyper,
-                                                           const uint8_t* __restrict__ mask64, int zero_grad) {
-    const AdamwCoef cd = adamw_coef(hyper, true), cn = adamw_coef(hyper, false);
+                                                           const uint8_t* __restrict__ mask64, const float* __restrict__ lr_scale,
+                                                           int zero_grad) {
+    [[maybe_unused]] const AdamwCoef cd = adamw_coef_uniform<SC>(hyper, true), cn = adamw_coef_uniform<SC>(hyper, false);
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < (int64_t)nblocks * 16; q += (int64_t)gridDim.x * 256) {
         const int blk = blocks[q >> 4];
         const int64_t i = (int64_t)blk * 16 + (q & 15);
@@ -278,7 +297,8 @@ __global__ __launch_bounds__(256) void adamw_kernel_blocks(float* __restrict__ p
         float4 pp = *(float4*)(p + i * 4);
         const float4 gg = *(const float4*)(g + i * 4);
         float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
-        adamw_step4(pp, mm, vv, gg, (mk & 1u) ? cd : cn);
+        if constexpr (SC) adamw_step4(pp, mm, vv, gg, adamw_coef(hyper, (mk & 1u) != 0, lr_scale[mk >> TULIP_LR_GROUP_SHIFT]));
+        else adamw_step4(pp, mm, vv, gg, (mk & 1u) ? cd : cn);
         *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
         if (zero_grad) *(float4*)(g + i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
         if (pb) *(uint2*)(pb + i * 4) = make_uint2(pack_bf16x2(pp.x, pp.y), pack_bf16x2(pp.z, pp.w));
@@ -430,13 +450,19 @@ extern "C" int tulip_reduce_rows_multi(const tulip_reduce_region* regions, int n
 
 extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions, int n, const tulip_adamw_ref* adam,
                                              hipStream_t stream) {
+    return tulip_reduce_rows_multi_adamw_s(regions, n, adam, nullptr, stream);
+}
+
+extern "C" int tulip_reduce_rows_multi_adamw_s(const tulip_reduce_region* regions, int n, const tulip_adamw_ref* adam,
+                                               const float* lr_scale64, hipStream_t stream) {
     if (n < 0 || n > TULIP_REDUCE_REGIONS_MAX || (n && !regions)) return TULIP_ERR_ARG;
     if (adam && (!adam->hyper || !adam->grad || !adam->param || !adam->exp_avg || !adam->exp_avg_sq || !adam->param_bf16))
         return TULIP_ERR_ARG;
+    if (lr_scale64 && (!adam || !adam->decay_mask64)) return TULIP_ERR_ARG;       // the group index lives in the mask bytes
     MultiRegions R;
     R.ad = adam ? AdamRef{adam->hyper, adam->grad, adam->param, adam->exp_avg, adam->exp_avg_sq, (bf16_t*)adam->param_bf16,
-                          adam->decay_mask64}
-                : AdamRef{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+                          adam->decay_mask64, lr_scale64}
+                : AdamRef{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     R.n = 0;
     int blocks = 0;
     MultiRegion wide[TULIP_REDUCE_REGIONS_MAX];     // scatter regions with LL = 1024 / 4096: scatter_bias_kernel
@@ -469,7 +495,8 @@ extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions,
         blocks += (int)((r.n4 + ct - 1) / ct);
     }
     if (blocks > 0) {
-        hipLaunchKernelGGL(reduce_rows_multi_kernel, dim3(blocks), dim3(256), 0, stream, R);
+        if (lr_scale64) hipLaunchKernelGGL(reduce_rows_multi_kernel<true>, dim3(blocks), dim3(256), 0, stream, R);
+        else hipLaunchKernelGGL(reduce_rows_multi_kernel<false>, dim3(blocks), dim3(256), 0, stream, R);
         TULIP_CHECK_LAUNCH();
     }
     for (int i = 0; i < nwide; ++i) {
@@ -514,20 +541,41 @@ extern "C" int tulip_l1_loss_bwd(const float* pred, const float* target, const f
 
 extern "C" int tulip_adamw(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_t n,
                            const float* hyper, const uint8_t* decay_mask64, int zero_grad, hipStream_t stream) {
+    return tulip_adamw_s(p, g, m, v, p_bf16, n, hyper, decay_mask64, nullptr, zero_grad, stream);
+}
+
+extern "C" int tulip_adamw_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, const float* hyper,
+                             const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad, hipStream_t stream) {
     if (n <= 0) return TULIP_OK;
     if (n & 3) return TULIP_ERR_ARG;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
-                       decay_mask64, zero_grad);
+    if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;         // the group index lives in the mask bytes
+    if (lr_scale64)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
+                           decay_mask64, lr_scale64, zero_grad);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
+                           decay_mask64, lr_scale64, zero_grad);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
 
 extern "C" int tulip_adamw_blocks(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
                                   const float* hyper, const uint8_t* decay_mask64, int zero_grad, hipStream_t stream) {
+    return tulip_adamw_blocks_s(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64, nullptr, zero_grad, stream);
+}
+
+extern "C" int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
+                                    const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
+                                    hipStream_t stream) {
     if (nblocks <= 0) return TULIP_OK;
     if (!p || !g || !m || !v || !blocks || !hyper) return TULIP_ERR_ARG;
-    hipLaunchKernelGGL(adamw_kernel_blocks, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
-                       (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, zero_grad);
+    if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;
+    if (lr_scale64)
+        hipLaunchKernelGGL(adamw_kernel_blocks<true>, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
+                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad);
+    else
+        hipLaunchKernelGGL(adamw_kernel_blocks<false>, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
+                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

@@ -649,7 +649,7 @@ constexpr int WG_LDS_BYTES = 2 * 5 * WG_SUB;  // double-buffered 4 x 1 stage (th
 #ifndef TULIP_WGRAD_LOAD_NT
 #define TULIP_WGRAD_LOAD_NT 1      // operand stream non-temporal: same-box A/B of the step 1.996 vs 2.014 ms (batch 8), batch 64 flat -- it ran the fused wide blocks' weights out of L2
 #endif
-template <int GM, int GN, int RING>
+template <int GM, int GN, int RING, bool SC>
 __device__ __forceinline__ void wgrad_tile(const GemmArgs& p, const int bx, const int by, const int bz,
                                            unsigned char* __restrict__ smem, const AdamRef& ad) {
     static_assert(GM * GN == 4, "four compute waves");
@@ -830,7 +830,11 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& p, const int bx, cons
     const bool split = p.epi == TULIP_EPI_SPLIT_F32;
     float* obase = (float*)p.out + (split ? (size_t)bz * p.M * p.ldo : 0);
     const bool step_here = !split && (p.accumulate & 2);               // (uniform) AdamW in the write-out, see AdamRef
-    const AdamwCoef cf = step_here ? adamw_coef(ad.hyper, true) : AdamwCoef{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // SC: at the learning-rate scale of the tensor's group -- one tensor per item, so the mask byte of its first block names it
+    const AdamwCoef cf = !step_here ? AdamwCoef{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f} : [&] {
+        if constexpr (SC) return adamw_coef(ad.hyper, true, ad.lr_scale[ad.mask64[(size_t)((const float*)p.out - ad.g0) >> 6] >> TULIP_LR_GROUP_SHIFT]);
+        else return adamw_coef(ad.hyper, true);
+    }();
 #pragma unroll
     for (int ps = 0; ps < 3; ++ps) {
 #pragma unroll
@@ -913,6 +917,7 @@ struct WgradGroup {
     int n;
     AdamRef adam;
 };
+template <bool SC>
 __global__ __launch_bounds__(512) void wgrad_group_kernel(const WgradGroup G) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[WG_LDS_BYTES];
     // workgroup b runs on XCD b % 8: neighbours in the (token chunk, tile) order -- tiles of one chunk share its
@@ -929,9 +934,9 @@ __global__ __launch_bounds__(512) void wgrad_group_kernel(const WgradGroup G) {
     const int by = b / G.gx[i], bx = b - by * G.gx[i];
     const GemmArgs p = G.g[i];
     switch (G.shape[i]) {
-        case 0: wgrad_tile<2, 2, 4>(p, bx, by, bz, smem, G.adam); break;
-        case 1: wgrad_tile<4, 1, 4>(p, bx, by, bz, smem, G.adam); break;
-        default: wgrad_tile<1, 4, 4>(p, bx, by, bz, smem, G.adam); break;
+        case 0: wgrad_tile<2, 2, 4, SC>(p, bx, by, bz, smem, G.adam); break;
+        case 1: wgrad_tile<4, 1, 4, SC>(p, bx, by, bz, smem, G.adam); break;
+        default: wgrad_tile<1, 4, 4, SC>(p, bx, by, bz, smem, G.adam); break;
     }
 }
 
@@ -1316,8 +1321,6 @@ extern "C" int tulip_gemm_bf16(const void* A, int lda, int a_trans, const void* 
     return TULIP_OK;
 }
 
-extern "C" int tulip_reduce_rows_multi_adamw(const tulip_reduce_region* regions, int n, const tulip_adamw_ref* adam,
-                                             hipStream_t stream);
 
 // tile shape of the large-tile weight-gradient kernel for a [Nw][Kw] gradient: 0 = 192 x 192, 1 = 384 x 96, 2 = 96 x 384,
 // -1 = none (the 64 x 96 tile of gemm_group_kernel)
@@ -1341,20 +1344,27 @@ extern "C" int tulip_wgrad_tiles(int Nw, int Kw, int flags) {
 }
 
 static int wgrad_group_impl(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
-                            void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam, void* prof,
-                            hipStream_t stream);
+                            void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam,
+                            const float* lr_scale64, void* prof, hipStream_t stream);
 
 extern "C" int tulip_wgrad_group(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
                                  void* workspace, int64_t workspace_bytes, int fold, hipStream_t stream) {
-    return wgrad_group_impl(items, n, extra, n_extra, workspace, workspace_bytes, fold, nullptr, nullptr, stream);
+    return wgrad_group_impl(items, n, extra, n_extra, workspace, workspace_bytes, fold, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tulip_wgrad_group_adamw(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
                                        void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam,
                                        hipStream_t stream) {
+    return tulip_wgrad_group_adamw_s(items, n, extra, n_extra, workspace, workspace_bytes, fold, adam, nullptr, stream);
+}
+
+extern "C" int tulip_wgrad_group_adamw_s(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
+                                         void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam,
+                                         const float* lr_scale64, hipStream_t stream) {
     if (adam && (!adam->hyper || !adam->grad || !adam->param || !adam->exp_avg || !adam->exp_avg_sq || !adam->param_bf16))
         return TULIP_ERR_ARG;
-    return wgrad_group_impl(items, n, extra, n_extra, workspace, workspace_bytes, fold, adam, nullptr, stream);
+    if (lr_scale64 && (!adam || !adam->decay_mask64)) return TULIP_ERR_ARG;       // the group index lives in the mask bytes
+    return wgrad_group_impl(items, n, extra, n_extra, workspace, workspace_bytes, fold, adam, lr_scale64, nullptr, stream);
 }
 
 // dev (tools/wgrad_phases.py): the grouped launch alone (no fold, no optimizer step) with 4 shader-clock stamps per workgroup
@@ -1363,12 +1373,12 @@ extern "C" int tulip_wgrad_group_profiled(const tulip_wgrad_item* items, int n, 
 #if !TULIP_DEV_VARIANTS
     return TULIP_ERR_NOT_BUILT;
 #endif
-    return wgrad_group_impl(items, n, nullptr, 0, workspace, workspace_bytes, flags & ~TULIP_WGRAD_FOLD, nullptr, stamps, stream);
+    return wgrad_group_impl(items, n, nullptr, 0, workspace, workspace_bytes, flags & ~TULIP_WGRAD_FOLD, nullptr, nullptr, stamps, stream);
 }
 
 static int wgrad_group_impl(const tulip_wgrad_item* items, int n, const tulip_reduce_region* extra, int n_extra,
-                            void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam, void* prof,
-                            hipStream_t stream) {
+                            void* workspace, int64_t workspace_bytes, int fold, const tulip_adamw_ref* adam,
+                            const float* lr_scale64, void* prof, hipStream_t stream) {
     if (n < 0 || n > GROUP_MAX || n_extra < 0 || n + n + n_extra > TULIP_REDUCE_REGIONS_MAX || (n && !items) ||
         (n_extra && !extra))
         return TULIP_ERR_ARG;
@@ -1390,6 +1400,8 @@ static int wgrad_group_impl(const tulip_wgrad_item* items, int n, const tulip_re
         if (it.Nw <= 0 || it.Kw <= 0 || it.Mtok <= 0) continue;
         if ((it.Mtok & 7) || (it.Nw & 7) || (it.Kw & 7) || (it.ldy & 7) || (it.ldx & 7) || !it.dY || !it.X || !it.dW)
             return TULIP_ERR_ARG;
+        // with a scale table the group of a stepped tensor is read from the mask byte of its first block: whole blocks only
+        if (lr_scale64 && it.reserved_ == 1 && adam && it.overwrite && ((it.dW - adam->grad) & 63)) return TULIP_ERR_ARG;
         int splits = it.splits < 1 ? 1 : it.splits;
         const int kchunk = (((it.Mtok + splits - 1) / splits) + BK - 1) / BK * BK;
         splits = (it.Mtok + kchunk - 1) / kchunk;
@@ -1424,10 +1436,11 @@ static int wgrad_group_impl(const tulip_wgrad_item* items, int n, const tulip_re
         const int blocks = G.first[G.n];
         if (big) {
             G.adam = adam ? AdamRef{adam->hyper, adam->grad, adam->param, adam->exp_avg, adam->exp_avg_sq, (bf16_t*)adam->param_bf16,
-                                    adam->decay_mask64}
-                          : AdamRef{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+                                    adam->decay_mask64, lr_scale64}
+                          : AdamRef{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
             for (int i = 0; i < G.n; ++i) G.g[i].aux = prof;
-            hipLaunchKernelGGL(wgrad_group_kernel, dim3(blocks), dim3(512), 0, stream, G);
+            if (lr_scale64) hipLaunchKernelGGL(wgrad_group_kernel<true>, dim3(blocks), dim3(512), 0, stream, G);
+            else hipLaunchKernelGGL(wgrad_group_kernel<false>, dim3(blocks), dim3(512), 0, stream, G);
         } else {
             GemmGroup S;
             S.n = G.n;
@@ -1442,7 +1455,7 @@ static int wgrad_group_impl(const tulip_wgrad_item* items, int n, const tulip_re
     }
     if (!(fold & TULIP_WGRAD_FOLD)) return TULIP_OK;
     for (int i = 0; i < n_extra; ++i) folds[nf++] = extra[i];
-    return nf ? tulip_reduce_rows_multi_adamw(folds, nf, adam, stream) : TULIP_OK;
+    return nf ? tulip_reduce_rows_multi_adamw_s(folds, nf, adam, lr_scale64, stream) : TULIP_OK;
 }
 
 // The fold regions tulip_wgrad_group(..., fold = 1) would pass to tulip_reduce_rows_multi for these items and this workspace

@@ -1353,6 +1353,8 @@ class TulipEngine:
             if self.adam_probe is not None:
                 self.adam_probe[out] = max(n, self.adam_probe.get(out, 0))
             kw["adamw"] = self.adam_apply and out in self.adam_fused
+            if kw["adamw"] and self.adam_sites is not None:
+                self.adam_sites[out] = "fold"
         r = ops.reduce_region(part, stride, out, n, rows, **kw)
         if self.overlap_wgrad:
             self._pending.append(("r", r))
@@ -1439,6 +1441,10 @@ class TulipEngine:
                 step_here = (elig and self.adam_apply and gout in self.adam_fused
                              and (sp == 1 or gbias is None or gbias in self.adam_fused))
                 any_adam = any_adam or step_here
+                if step_here and self.adam_sites is not None:
+                    self.adam_sites[gout] = "fold" if sp > 1 else "writeout"
+                    if sp > 1 and gbias is not None:
+                        self.adam_sites[gbias] = "fold"
                 grp.append(ops.wgrad_item(dY, ldy, X, ldx, Nw, Kw, Mtok, gout, gbias, sp, overwrite=self.grad_overwrite,
                                           adamw=step_here))
                 items.pop(0)
@@ -1802,6 +1808,7 @@ class TulipEngine:
     adam_fused = frozenset()
     adam_apply = False
     adam_probe = None
+    adam_sites = None            # a dict (Trainer.adamw_sites): gradient address -> "writeout" | "fold", filled as the stepping launches are issued
     _gflat = None
     fuse_adamw_folds = True      # (False: only the un-split write-outs step)
 
@@ -2074,6 +2081,8 @@ class TulipEngine:
                 if self.adam_probe is not None:
                     self.adam_probe[gpe] = max(P.embed_stride, self.adam_probe.get(gpe, 0))
                 kw["adamw"] = self.adam_apply and gpe in self.adam_fused
+                if kw["adamw"] and self.adam_sites is not None:
+                    self.adam_sites[gpe] = "fold"
             ops.reduce_rows_multi([ops.reduce_region(ep, P.embed_stride, gpe, P.embed_stride, nbe, **kw)], adam=self._adam_arg())
         if self.pack_at_end and self.adam_apply and self._pack_ev is None:
             # the marked group has not been enqueued (its fork is still deferred: the marked tag is this last stage, e.g. a model

@@ -104,10 +104,40 @@ def wgrad_item(dY, ldy, X, ldx, Nw, Kw, Mtok, dW, db=None, splits=1, overwrite=F
     return _lib.WgradItem(_p(dY), _p(X), _p(dW), _p(db), ldy, ldx, Nw, Kw, Mtok, splits, int(overwrite), int(adamw))
 
 
-def adamw_ref(hyper, grad, param, exp_avg, exp_avg_sq, param_bf16, decay_mask64=None):
+def adamw_ref(hyper, grad, param, exp_avg, exp_avg_sq, param_bf16, decay_mask64=None, lr_scale64=None):
     """tulip_adamw_ref: the flat buffers tulip_wgrad_group_adamw / tulip_reduce_rows_multi_adamw step in (all laid out like
-    `grad`); decay_mask64: tulip_adamw's mask (bit 0: weight decay for these 64 elements; None: everywhere)."""
-    return _lib.AdamwRef(_p(hyper), _p(grad), _p(param), _p(exp_avg), _p(exp_avg_sq), _p(param_bf16), _p(decay_mask64))
+    `grad`); decay_mask64: tulip_adamw's mask (bit 0: weight decay for these 64 elements; None: everywhere).
+    lr_scale64 (needs the mask): the 64-float table of per-group learning-rate scales, group = mask byte >> 2 -- it rides on the
+    returned object and sends wgrad_group / reduce_rows_multi to the `_s` entry points."""
+    if lr_scale64 is not None and decay_mask64 is None:
+        raise ValueError("lr_scale64 needs decay_mask64: the group index lives in bits 2-7 of the mask bytes")
+    ref = _lib.AdamwRef(_p(hyper), _p(grad), _p(param), _p(exp_avg), _p(exp_avg_sq), _p(param_bf16), _p(decay_mask64))
+    ref.lr_scale64 = _p(lr_scale64)
+    return ref
+
+
+def pack_lr_groups(decay_mask64: torch.Tensor, block_scale) -> tuple:
+    """The carrier of per-parameter learning-rate scales: (mask bytes, table).  `block_scale`: one float per 64-float block
+    (a sequence or 1-d tensor as long as the mask).  The scales are quantised to float32 and their distinct values numbered --
+    1.0 is always group 0 --; a block's group goes into bits 2-7 of its mask byte, bits 0 (decay) and 1 (stepped elsewhere) stay
+    as they are, and table[group] is the scale (64 float32 on the CPU, unused entries 1.0).  More than 64 distinct scales:
+    ValueError."""
+    sc = torch.as_tensor(block_scale, dtype=torch.float32).reshape(-1).cpu()
+    mask = decay_mask64.detach().cpu()
+    if mask.dtype != torch.uint8 or mask.numel() != sc.numel():
+        raise ValueError("pack_lr_groups: one uint8 mask byte and one scale per 64-float block")
+    if not bool(torch.isfinite(sc).all()) or bool((sc < 0).any()):
+        raise ValueError("learning-rate scales must be finite and >= 0")
+    values = [1.0] + sorted(set(sc.tolist()) - {1.0}, reverse=True)
+    if len(values) > _lib.LR_GROUPS_MAX:
+        raise ValueError(f"{len(values)} distinct learning-rate scales (1.0 included): the fused AdamW carries at most "
+                         f"{_lib.LR_GROUPS_MAX} groups (bits 2-7 of the decay mask bytes)")
+    table = torch.ones(_lib.LR_GROUPS_MAX, dtype=torch.float32)
+    table[:len(values)] = torch.tensor(values, dtype=torch.float32)
+    group = torch.zeros_like(mask)
+    for gi, val in enumerate(values):
+        group[sc == val] = gi
+    return (mask & 3) | (group << _lib.LR_GROUP_SHIFT), table
 
 
 def reduce_rows_multi(regions, adam=None):
@@ -116,6 +146,9 @@ def reduce_rows_multi(regions, adam=None):
     arr = (_lib.ReduceRegion * max(len(regions), 1))(*regions)
     if adam is None:
         check(_lib.load().tulip_reduce_rows_multi(arr, len(regions), _stream()), "tulip_reduce_rows_multi")
+    elif getattr(adam, "lr_scale64", None) is not None:
+        check(_lib.load().tulip_reduce_rows_multi_adamw_s(arr, len(regions), ctypes.byref(adam), adam.lr_scale64, _stream()),
+              "tulip_reduce_rows_multi_adamw_s")
     else:
         check(_lib.load().tulip_reduce_rows_multi_adamw(arr, len(regions), ctypes.byref(adam), _stream()),
               "tulip_reduce_rows_multi_adamw")
@@ -144,6 +177,9 @@ def wgrad_group(items, extra, workspace, workspace_bytes, fold=True, adam=None, 
     if adam is None:
         check(_lib.load().tulip_wgrad_group(ia, len(items), ea, len(extra), _p(workspace), workspace_bytes, int(fold),
                                             _stream()), "tulip_wgrad_group")
+    elif getattr(adam, "lr_scale64", None) is not None:
+        check(_lib.load().tulip_wgrad_group_adamw_s(ia, len(items), ea, len(extra), _p(workspace), workspace_bytes, int(fold),
+                                                    ctypes.byref(adam), adam.lr_scale64, _stream()), "tulip_wgrad_group_adamw_s")
     else:
         check(_lib.load().tulip_wgrad_group_adamw(ia, len(items), ea, len(extra), _p(workspace), workspace_bytes, int(fold),
                                                   ctypes.byref(adam), _stream()), "tulip_wgrad_group_adamw")
@@ -318,13 +354,23 @@ def l1_loss_bwd(pred, target, gscale_dev, gscale, dpred, n):
                                         _stream()), "tulip_l1_loss_bwd")
 
 
-def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False):
+def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None):
+    """lr_scale64: per-group learning-rate scales (pack_lr_groups; tulip_adamw_s) -- None: tulip_adamw."""
+    if lr_scale64 is not None:
+        check(_lib.load().tulip_adamw_s(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(hyper), _p(decay_mask64),
+                                        _p(lr_scale64), int(zero_grad), _stream()), "tulip_adamw_s")
+        return
     check(_lib.load().tulip_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(hyper), _p(decay_mask64),
                                   int(zero_grad), _stream()), "tulip_adamw")
 
 
-def adamw_blocks(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64=None, zero_grad=False):
+def adamw_blocks(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None):
     """tulip_adamw over the listed 64-float blocks only (blocks: int32 device tensor of block indices)."""
+    if lr_scale64 is not None:
+        check(_lib.load().tulip_adamw_blocks_s(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(blocks), nblocks, _p(hyper),
+                                               _p(decay_mask64), _p(lr_scale64), int(zero_grad), _stream()),
+              "tulip_adamw_blocks_s")
+        return
     check(_lib.load().tulip_adamw_blocks(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(blocks), nblocks, _p(hyper),
                                          _p(decay_mask64), int(zero_grad), _stream()), "tulip_adamw_blocks")
 

@@ -36,12 +36,31 @@ def cosine_lr(epoch_float: float, lr: float, min_lr: float, warmup_epochs: float
                                                           / (epochs - warmup_epochs)))
 
 
+def layer_decay_scales(model, layer_decay: float = 0.75, layers_per_group: int = 12) -> dict:
+    """{parameter name: lr_scale} of layer-wise learning-rate decay, for `Trainer(lr_scales=...)`: the reference builds its
+    optimizer from timm's `optim_factory.param_groups_layer_decay(model, weight_decay)` (main_lidar_upsampling.py:282, timm's
+    default layer_decay = 0.75) and its schedule sets `lr * lr_scale` per group at every iteration (util/lr_sched.py:16-20).
+    The rule, for a model without a `group_matcher` and without a `pretrained_cfg` classifier (TULIP has neither):
+      1. the names of the parameters with requires_grad, in named_parameters() order;
+      2. consecutive chunks of `layers_per_group` names are the groups (the last may be shorter), G groups in all;
+      3. group i gets layer_decay ** (G - 1 - i).
+    tulip_base: 212 names, 18 groups, 0.75**17 = 0.0075 for the first 12 tensors up to 1.0 for the last 8.
+    CAVEAT: timm is neither installed beside this package nor part of the reference tree; the rule is restated from timm's
+    source from memory and is not pinned by any test against timm itself.  The function is pure in its three arguments: with
+    another timm version, pass that version's own groups (`Trainer(lr_scales=param_groups)`) instead."""
+    if layers_per_group < 1:
+        raise ValueError("layers_per_group must be >= 1")
+    names = [n for n, p in model.named_parameters() if p.requires_grad]
+    G = (len(names) + layers_per_group - 1) // layers_per_group
+    return {n: float(layer_decay) ** (G - 1 - i // layers_per_group) for i, n in enumerate(names)}
+
+
 class Trainer:
     def __init__(self, model, batch_size: int, lr: float = 5e-4, betas=(0.9, 0.95), eps: float = 1e-8,
                  weight_decay: float = 0.01, device=None, use_graph: bool = True, process_group=None,
                  bucket_mb: float = 16.0, accum_iter: int = 1, track_grad_norm: bool = False,
                  force_segments: bool = False, bucket_adamw: Optional[bool] = None, grad_dtype: str = "fp32",
-                 attn_fp8: Optional[bool] = None, exchange: str = "allreduce"):
+                 attn_fp8: Optional[bool] = None, exchange: str = "allreduce", lr_scales=None):
         """force_segments: run the N>1 step structure (graph segments cut at the bucket points, one all-reduce per
         bucket between replays) in a one-rank process group too -- how the RCCL path is exercised on a single GPU.
         bucket_adamw: None = environment default (TULIP_BUCKET_ADAMW, off).
@@ -51,7 +70,12 @@ class Trainer:
         exchange: "allreduce" (default) or "sharded" (tulip_amd.ddp.ShardedExchange, round 5; optional, never measured on more
         than one GPU): per bucket reduce-scatter -> AdamW on the owned shard and on the parameters the kernels read in fp32 ->
         all-gather of the bf16 shadow, on the optimizer stream beside the rest of the backward.  The fp32 master and the moments
-        are then current only where this rank steps them: gather_state() (called by state_dict()) makes them whole."""
+        are then current only where this rank steps them: gather_state() (called by state_dict()) makes them whole.
+        lr_scales: per-parameter learning-rate scales (layer-wise lr decay; `layer_decay_scales(model)` is the reference's
+        recipe): {parameter name: float} -- names left out get 1.0, unknown names raise KeyError -- or a list of torch-style
+        param groups carrying `lr_scale`.  Every AdamW site steps a tensor at fl32(lr * scale); at most 64 distinct scales
+        (ValueError beyond); exchange="sharded" with scales other than 1.0 raises ValueError (that plan is optional and
+        unmeasured).  `step(lr=...)` keeps setting the unscaled rate."""
         self.model = model
         device = device or torch.device("cuda", torch.cuda.current_device())
         self.device = device
@@ -140,7 +164,12 @@ class Trainer:
                            and knobs.on("TULIP_FUSE_ADAMW", True))
         self._adam_mask = None
         self._adam_blocks = None
+        # per-parameter learning-rate scales: the group of every 64-float block in bits 2-7 of this Trainer's copy of the decay mask,
+        # the scales in a 64-float device table (None while every scale is 1.0: the launches then are the ones without a table)
+        self.lr_scales = {n: 1.0 for n in W.names}
+        self._mask, self._lr_table = W.decay_mask, None
         self._adam_ctx, self._adam_fused = None, frozenset()
+        self._adam_names, self._adam_sites = {}, {}
         self.fused_adamw_params = 0
         # parity tests: explicit DropPath uniforms [n_drop_slots][B] (device tensor) instead of the counter-based draws;
         # set before the first step (the choice is baked into the captured graphs)
@@ -174,7 +203,48 @@ class Trainer:
             src = 0 if process_group is None else dist.get_global_rank(process_group, 0)
             dist.broadcast(W.flat, src=src, group=process_group)
             self.eng.wgrad_ctas = self.eng.WGRAD_DDP_CTAS      # leave the CUs RCCL's channels sit on out of a round
+        if lr_scales is not None:
+            self.set_lr_scales(lr_scales)
         W.refresh_shadow()
+
+    # ------------------------------------------------------------------ per-parameter learning-rate scales
+    def _scales_by_name(self, lr_scales) -> dict:
+        W = self.eng.params
+        out = {n: 1.0 for n in W.names}
+        if isinstance(lr_scales, dict):
+            unknown = [n for n in lr_scales if n not in out]
+            if unknown:
+                raise KeyError(f"lr_scales names {len(unknown)} parameters this model does not have, e.g. {unknown[:3]}")
+            out.update({n: float(v) for n, v in lr_scales.items()})
+            return out
+        by_ptr = self._param_names_by_ptr()
+        for grp in lr_scales:                      # torch-style param groups
+            for p in grp["params"]:
+                n = by_ptr.get(p.data_ptr())
+                if n is None:
+                    raise KeyError("lr_scales holds a parameter that is not one of this model's (was the model moved?)")
+                out[n] = float(grp.get("lr_scale", 1.0))
+        return out
+
+    def set_lr_scales(self, lr_scales) -> None:
+        """Install per-parameter learning-rate scales (see __init__; None: all 1.0): quantised to float32, numbered, written
+        into the mask bytes and the device table once.  A captured step is captured again."""
+        W = self.eng.params
+        by_name = self._scales_by_name(lr_scales if lr_scales is not None else {})
+        blocks = torch.ones(W.total // ALIGN, dtype=torch.float32)
+        for n in W.names:
+            blocks[W.offset[n] // ALIGN:(W.offset[n] + W.numel[n] + ALIGN - 1) // ALIGN] = by_name[n]
+        mask, table = ops.pack_lr_groups(W.decay_mask, blocks)
+        trivial = bool((mask >> 2 == 0).all())
+        if not trivial and self.exchange == "sharded":
+            raise ValueError("exchange='sharded' with learning-rate scales other than 1.0 is not supported: use exchange='allreduce'")
+        self.lr_scales = {n: float(torch.tensor(by_name[n], dtype=torch.float32)) for n in W.names}
+        self._mask = W.decay_mask if trivial else mask.to(self.device)
+        self._lr_table = None if trivial else table.to(self.device)
+        # the fused plan's mask and table are launch arguments baked into the captured graphs
+        self._adam_mask, self._adam_blocks, self._adam_ctx, self._adam_fused = None, None, None, frozenset()
+        self._adam_names, self._adam_sites = {}, {}
+        self._segments = None
 
     # ------------------------------------------------------------------ pieces
     def _set_hyper(self):
@@ -198,9 +268,9 @@ class Trainer:
         # the fused-AdamW plan points at THIS trainer's gradient / moment / mask buffers: a second Trainer on the same model
         # (another batch size, a rebuild) must not leave its own on the engine for this one's launches or captures
         if getattr(self, "_adam_ctx", None) is not None:
-            eng.adam_fused, eng.adam_ctx = self._adam_fused, self._adam_ctx
+            eng.adam_fused, eng.adam_ctx, eng.adam_sites = self._adam_fused, self._adam_ctx, self._adam_sites
         elif eng.adam_probe is None:
-            eng.adam_fused, eng.adam_ctx = frozenset(), None
+            eng.adam_fused, eng.adam_ctx, eng.adam_sites = frozenset(), None, None
         # (the flat gradient buffer is cleared by the fused AdamW right after it consumed it)
         eng.draw_drop_scales(P, self.model.training, self.inject_drop_u)
         eng.run_forward(P, pack_on_side=self.pack_at_step_start, defer_loss_final=True)
@@ -213,7 +283,7 @@ class Trainer:
         W = self.eng.params
         ops.adamw(W.base32 + 4 * lo, self.g.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo,
                   self.v.data_ptr() + 4 * lo, W.base16 + 2 * lo, hi - lo, self.hyper,
-                  W.decay_mask.data_ptr() + lo // 64, zero_grad=not self.grad_overwrite)
+                  self._mask.data_ptr() + lo // 64, zero_grad=not self.grad_overwrite, lr_scale64=self._lr_table)
 
     def _cast_bucket_down(self, tag):
         """grad_dtype bf16: the bucket's gradients -> the bf16 exchange buffer (captured at the end of the bucket's graph
@@ -294,13 +364,14 @@ class Trainer:
         if self.track_grad_norm:
             # g holds the SUM over ranks here; hyper[7] = 1/world turns it into DDP's mean
             ops.grad_norm(self.g, W.total, self._norm_part, self.grad_norm, scale_dev=self.hyper[7:8])
-        mask = self._adam_mask if self._adam_mask is not None else W.decay_mask       # (bit 1: stepped beside the backward)
+        mask = self._adam_mask if self._adam_mask is not None else self._mask         # (bit 1: stepped beside the backward)
         if self._adam_blocks is not None:
             # most tensors were stepped where their gradient was completed: the few blocks left, by index (nothing scanned)
             ops.adamw_blocks(W.flat, self.g, self.m, self.v, W.shadow, self._adam_blocks, self._adam_blocks.numel(), self.hyper,
-                             mask, zero_grad=not self.grad_overwrite)
+                             mask, zero_grad=not self.grad_overwrite, lr_scale64=self._lr_table)
         else:
-            ops.adamw(W.flat, self.g, self.m, self.v, W.shadow, W.total, self.hyper, mask, zero_grad=not self.grad_overwrite)
+            ops.adamw(W.flat, self.g, self.m, self.v, W.shadow, W.total, self.hyper, mask, zero_grad=not self.grad_overwrite,
+                      lr_scale64=self._lr_table)
         if self._pack_at_end:
             if W.pk_late:
                 W.refresh_transposes(late=True)
@@ -314,7 +385,7 @@ class Trainer:
         self.gather_state()
         cut = lambda flat, n: flat[W.offset[n]:W.offset[n] + W.numel[n]].view(W.shape[n]).clone()
         return {"step": self.t, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
-                "weight_decay": self.wd, "accum_iter": self.accum_iter,
+                "weight_decay": self.wd, "accum_iter": self.accum_iter, "lr_scales": dict(self.lr_scales),
                 "exp_avg": {n: cut(self.m, n) for n in W.names}, "exp_avg_sq": {n: cut(self.v, n) for n in W.names},
                 "grad": {n: cut(self.g, n) for n in W.names} if self.micro % self.accum_iter else None,
                 "drop_seed": int(self.eng._drop_seed), "drop_counter": int(self.eng._drop_counter.item()),
@@ -337,6 +408,9 @@ class Trainer:
                 put(self.g, n, sd["grad"][n])
         self.t, self.micro, self.lr = int(sd["step"]), int(sd["micro"]), float(sd["lr"])
         self.betas, self.eps, self.wd = tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
+        saved = sd.get("lr_scales")                # (a dictionary saved before the scales existed: all ones)
+        if (saved if saved is not None else {n: 1.0 for n in W.names}) != self.lr_scales:
+            self.set_lr_scales(saved)
         # DropPath stream.  Same rank as the one that saved (or a checkpoint without a rank): the saved seed -- the resume then
         # continues the uninterrupted run's draws.  Another rank: the reference seeds rank r with seed + r (main_lidar_upsampling.py:
         # 155); when this engine's own seed sits at exactly that distance from the saved one the convention holds and the own seed
@@ -365,7 +439,8 @@ class Trainer:
         W = self.eng.params
         gbase = self.g.data_ptr()
         by_off = {W.offset[n]: n for n in W.names}
-        fused, mask, count = set(), W.decay_mask.clone(), 0
+        fused, mask, count = set(), self._mask.clone(), 0
+        self._adam_names, self._adam_sites = {}, {}
         cand, rejected_modules = [], set()
         module_of = lambda n: n.rsplit(".", 1)[0]
         for ptr, cnt in eligible.items():
@@ -386,13 +461,15 @@ class Trainer:
             if any(module_of(n) in rejected_modules for n in names):
                 continue
             fused.add(ptr)
+            self._adam_names[ptr] = list(names)
             mask[a // 64:(a + cnt + 63) // 64] |= 2
             count += sum(W.numel[n] for n in names)
         if fused:
             self._adam_fused = frozenset(fused)
             self._adam_mask = mask
-            self._adam_ctx = ops.adamw_ref(self.hyper, self.g, W.flat, self.m, self.v, W.shadow, decay_mask64=mask)
-            self.eng.adam_fused, self.eng.adam_ctx = self._adam_fused, self._adam_ctx
+            self._adam_ctx = ops.adamw_ref(self.hyper, self.g, W.flat, self.m, self.v, W.shadow, decay_mask64=mask,
+                                           lr_scale64=self._lr_table)
+            self.eng.adam_fused, self.eng.adam_ctx, self.eng.adam_sites = self._adam_fused, self._adam_ctx, self._adam_sites
             self.fused_adamw_params = count
             if self._want_pack_at_end and getattr(W, "pk_offset", None):
                 packed = W.packed_names()
@@ -408,6 +485,19 @@ class Trainer:
             if 0 < left.numel() * 64 <= W.total // 4:       # (a long list gains nothing over the scan)
                 self._adam_blocks = left.contiguous()
 
+    def adamw_sites(self) -> dict:
+        """{parameter name: site} of the plan the last optimizer step ran: which of the four places that take the AdamW step
+        stepped the tensor -- "writeout" (tulip_wgrad_group_adamw: the weight-gradient write-out), "fold"
+        (tulip_reduce_rows_multi_adamw), "blocks" (tulip_adamw_blocks) or "scan" (tulip_adamw).  exchange="sharded" steps
+        through tulip_adamw_blocks on every rank's own shard and is not described here."""
+        W = self.eng.params
+        rest = "blocks" if self._adam_blocks is not None else "scan"
+        out = {n: rest for n in W.names}
+        for ptr, names in self._adam_names.items():
+            if ptr in self._adam_fused and ptr in self._adam_sites:
+                out.update({n: self._adam_sites[ptr] for n in names})
+        return out
+
     # ------------------------------------------------------------------ torch.optim.AdamW <-> fused AdamW state
     def _param_names_by_ptr(self):
         W = self.eng.params
@@ -417,10 +507,22 @@ class Trainer:
         """Continue a run of the reference's optimizer (main_lidar_upsampling.py:283: torch.optim.AdamW over the module's
         parameters; a reference checkpoint's 'optimizer' entry after `optimizer.load_state_dict`, misc.py:386-390) with the
         fused step: exp_avg / exp_avg_sq / step of every parameter, lr, betas, eps and the weight decay of the decaying
-        group.  Parameters are matched by storage (the module's parameters are views of the flat buffer)."""
+        group.  Parameters are matched by storage (the module's parameters are views of the flat buffer).
+        Learning rates: every group's `lr_scale` (timm's param_groups_layer_decay) becomes the scale of its parameters and
+        self.lr the unscaled rate, lr / lr_scale of the group with the largest scale; groups without `lr_scale` get their lr
+        relative to the largest group lr, which becomes self.lr."""
         W, by_ptr = self.eng.params, self._param_names_by_ptr()
-        seen, steps, wds = set(), set(), set()
-        for grp in optimizer.param_groups:
+        seen, steps, wds, scales = set(), set(), set(), {}
+        groups = optimizer.param_groups
+        if any("lr_scale" in grp for grp in groups):
+            top = max(groups, key=lambda grp: float(grp.get("lr_scale", 1.0)))
+            top_scale = float(top.get("lr_scale", 1.0))
+            base_lr = float(top["lr"]) / top_scale if top_scale > 0.0 else float(top["lr"])
+            scale_of = lambda grp: float(grp.get("lr_scale", 1.0))
+        else:
+            base_lr = max(float(grp["lr"]) for grp in groups)
+            scale_of = lambda grp: float(grp["lr"]) / base_lr if base_lr > 0.0 else 1.0
+        for grp in groups:
             for p in grp["params"]:
                 n = by_ptr.get(p.data_ptr())
                 if n is None:
@@ -438,10 +540,12 @@ class Trainer:
                 elif float(grp["weight_decay"]) != 0.0:
                     raise ValueError("the fused AdamW decays ndim > 1 parameters only (timm's grouping, main:282)")
                 seen.add(n)
+                scales[n] = scale_of(grp)
         if seen != set(W.names) or len(steps) != 1 or len(wds) > 1:
             raise ValueError(f"cannot import: {len(W.names) - len(seen)} parameters missing, steps {sorted(steps)}, decays {sorted(wds)}")
         g0 = optimizer.param_groups[0]
-        self.t, self.lr, self.betas, self.eps = steps.pop(), float(g0["lr"]), tuple(g0["betas"]), float(g0["eps"])
+        self.set_lr_scales(scales)
+        self.t, self.lr, self.betas, self.eps = steps.pop(), base_lr, tuple(g0["betas"]), float(g0["eps"])
         if wds:
             self.wd = wds.pop()
         self.g.zero_()
@@ -450,10 +554,19 @@ class Trainer:
 
     def export_torch_optimizer(self, optimizer: "torch.optim.Optimizer") -> None:
         """The reverse: write the fused optimizer's moments and step count into a torch.optim.AdamW built over the module's
-        parameters (so that `optimizer.state_dict()` is what misc.save_model stores, misc.py:339-345)."""
+        parameters (so that `optimizer.state_dict()` is what misc.save_model stores, misc.py:339-345).  Every group gets
+        lr = lr * lr_scale (what the reference's schedule leaves there, util/lr_sched.py:16-20) and, where the scale is not 1.0
+        or the group already has the key, `lr_scale`; a group whose parameters do not share one scale raises ValueError."""
         W, by_ptr = self.eng.params, self._param_names_by_ptr()
         for grp in optimizer.param_groups:
-            grp["lr"], grp["betas"], grp["eps"] = self.lr, tuple(self.betas), self.eps
+            sc = {self.lr_scales[by_ptr[p.data_ptr()]] for p in grp["params"]}
+            if len(sc) > 1:
+                raise ValueError(f"cannot export: a param group mixes the learning-rate scales {sorted(sc)[:4]}; build the "
+                                 "optimizer over groups that share one scale (e.g. one group per lr_scale and weight decay)")
+            scale = sc.pop() if sc else 1.0
+            grp["lr"], grp["betas"], grp["eps"] = self.lr * scale, tuple(self.betas), self.eps
+            if scale != 1.0 or "lr_scale" in grp:
+                grp["lr_scale"] = scale
             for p in grp["params"]:
                 n = by_ptr[p.data_ptr()]
                 sl = slice(W.offset[n], W.offset[n] + W.numel[n])
@@ -654,6 +767,9 @@ class Trainer:
                 self.bucketer.prime(self.g if self.gb is None else self.gb)
             scratch = torch.zeros(64, dtype=torch.float32, device=self.device)
             ops.adamw(scratch, scratch.clone(), scratch.clone(), scratch.clone(), None, 64, self.hyper, None)
+            if self._lr_table is not None:
+                ops.adamw(scratch, scratch.clone(), scratch.clone(), scratch.clone(), None, 64, self.hyper,
+                          torch.zeros(1, dtype=torch.uint8, device=self.device), lr_scale64=self._lr_table)
             ops.grad_norm(scratch, 64, self._norm_part, self.grad_norm)
             self.g.copy_(keep_g)
             self.eng._drop_counter.copy_(keep_c)

@@ -206,8 +206,10 @@ __global__ __launch_bounds__(256) void ln_bwd_params_kernel(const bf16_t* __rest
             for (int u = 0; u < UNR; ++u) {
                 const float d0 = bf2f((bf16_t)(d[u].x & 0xffff)), d1 = bf2f((bf16_t)(d[u].x >> 16));
                 const float d2 = bf2f((bf16_t)(d[u].y & 0xffff)), d3 = bf2f((bf16_t)(d[u].y >> 16));
-                a[0] += d0 * (xv[u].x - mu[u]) * rs[u]; a[1] += d1 * (xv[u].y - mu[u]) * rs[u];
-                a[2] += d2 * (xv[u].z - mu[u]) * rs[u]; a[3] += d3 * (xv[u].w - mu[u]) * rs[u];
+                // dy * xhat with xhat = (x - mean) * rstd formed first, as the forward and ln_bwd_kernel form it ((dy * (x - mean))
+                // * rstd rounds dy * 1000 before the scale: one ulp off on rows of +-1e3, where xhat is exactly +-1)
+                a[0] += d0 * ((xv[u].x - mu[u]) * rs[u]); a[1] += d1 * ((xv[u].y - mu[u]) * rs[u]);
+                a[2] += d2 * ((xv[u].z - mu[u]) * rs[u]); a[3] += d3 * ((xv[u].w - mu[u]) * rs[u]);
                 a[4] += d0; a[5] += d1; a[6] += d2; a[7] += d3;
             }
         }

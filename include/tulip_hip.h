@@ -46,8 +46,9 @@ typedef struct ihipStream_t* hipStream_t;
 #define TULIP_EPI_SPLIT_F32 7    /* out_f32[split][M][ldo] = acc : split-K partial slabs (deterministic) */
 #define TULIP_EPI_UNSHUF2_BF16 8 /* inverse of 5, bf16: row m = fine token (b,2h+i,2w+j), column c -> out[(b,h,w)][4c+2i+j]
                                     with psH, psW = the COARSE grid, N = fine channels (backward of PixelShuffle(2)) */
-/* TULIP_EPI_F32 / TULIP_EPI_RESID_F32 with out2 != NULL and ldo2 > 0 additionally store bf16(result * rowscale)
- * at out2[m*ldo2 + n] (the operand of the next GEMM on the path); TULIP_EPI_PIXSHUF2_F32 stores fp32 to `out`
+/* TULIP_EPI_F32 with out2 != NULL and ldo2 > 0 additionally stores bf16(result * rowscale[m/rows_per_sample]) at
+ * out2[m*ldo2 + n] (the operand of the next GEMM on the path, entering a DropPath branch); TULIP_EPI_RESID_F32 stores
+ * bf16(result) there (the row scale is already inside the result); TULIP_EPI_PIXSHUF2_F32 stores fp32 to `out`
  * and/or bf16 to `out2` (row pitch ldo2), whichever is non-NULL. */
 
 /* C[M,N] = opA[M,K] . opB[N,K]^T, bf16 in / fp32 accumulate on v_mfma_f32_16x16x32_bf16.
@@ -60,7 +61,9 @@ typedef struct ihipStream_t* hipStream_t;
  * applies the epilogue.  workspace may be NULL when splits == 1.
  * Weight-gradient form (a_trans=1, epi SPLIT_F32 or F32): if out2 != NULL it additionally receives
  * the row sums of opA, i.e. sum over tokens of dY = the bias gradient, as fp32 [splits][M] (SPLIT) or
- * [M] (F32, += when accumulate) -- computed by one extra MFMA per fragment against an all-ones operand.
+ * [M] (F32, += when accumulate) -- computed by one extra MFMA per fragment against an all-ones operand.  They come out of the
+ * GEMM kernel's own k loop: TULIP_EPI_F32 with out2 (ldo2 = 0) and an effective split count above 1 is TULIP_ERR_ARG (take the
+ * slabs with TULIP_EPI_SPLIT_F32 and fold them).
  * `accumulate` is a flag word: TULIP_GEMM_ACCUMULATE (bit 0, the 0 / 1 of earlier versions); TULIP_GEMM_NO_TOUCH: skip the
  * split first touch of the cold [96][k range] weight panel that the M-tile workgroups of an N panel perform before their k
  * loops (forward / data-gradient form); TULIP_GEMM_CHECKED: the bounds-checked kernels even where whole tiles allow the
@@ -176,6 +179,34 @@ int tulip_wgrad_group_profiled(const tulip_wgrad_item* items, int n, void* works
 /* number of K-splits tulip_gemm_bf16 actually launches for (K, splits): K is cut in multiples of 32 */
 int tulip_gemm_effective_splits(int K, int splits);
 int tulip_gemm_packed_supported(int M, int N, int K, int splits);
+/* Which kernel tulip_gemm_bf16 launches for these arguments (host code only; `accumulate` is the call's flag word, of which
+ * TULIP_GEMM_CHECKED, TULIP_GEMM_MID and TULIP_GEMM_B_PACKED matter): the launcher takes its decision from the same function, so
+ * the answer cannot drift from the dispatch.  Returns TULIP_ERR_ARG where tulip_gemm_bf16 refuses on shape or flag grounds (K % 8,
+ * N % 8, M % 8 with a_trans, a packed B where the small-K form does not exist, a fold of 2^31 or more 8-column chunks) and for an
+ * empty shape (nothing is launched); pitches and pointers are not its business.  Otherwise a non-negative bit field:
+ *   bits 0-1  family   TULIP_ROUTE_TILE   gemm_kernel: BM x 96 tiles, bounds-checked loads and stores
+ *                      TULIP_ROUTE_FULL   gemm_kernel_full: the same tiles unchecked (whole tiles, a_trans = 0)
+ *                      TULIP_ROUTE_MID    gemm_mid_kernel: 192 x 192, 64-deep stages (TULIP_GEMM_MID where it fits)
+ *                      TULIP_ROUTE_STREAM gemm_stream_kernel: 32 x 96, the packed-B small-K form
+ *   bits 2-3  variant  tile families: tile rows 0 = 64, 1 = 128, 2 = 256 (256 only with a_trans = 0); stream: K per split
+ *                      0 = 96, 1 = 384, 2 = 768, 3 = 1536; mid: 0
+ *   bit  4    TULIP_ROUTE_DEEP     128-deep k stages instead of 32-deep ones (64-row tiles only)
+ *   bit  5    TULIP_ROUTE_A_TRANS  bit 6  TULIP_ROUTE_B_TRANS   the operand layouts the kernel is instantiated for
+ *   bit  7    TULIP_ROUTE_FOLD     splitk_epilogue_kernel follows (splits > 1 with an epilogue other than TULIP_EPI_SPLIT_F32)
+ *   bits 8-30 the K splits launched (= tulip_gemm_effective_splits(K, splits)) */
+#define TULIP_ROUTE_TILE 0
+#define TULIP_ROUTE_FULL 1
+#define TULIP_ROUTE_MID 2
+#define TULIP_ROUTE_STREAM 3
+#define TULIP_ROUTE_FAMILY(r) ((r) & 3)
+#define TULIP_ROUTE_VARIANT(r) (((r) >> 2) & 3)
+#define TULIP_ROUTE_DEEP 0x10
+#define TULIP_ROUTE_A_TRANS 0x20
+#define TULIP_ROUTE_B_TRANS 0x40
+#define TULIP_ROUTE_FOLD 0x80
+#define TULIP_ROUTE_SPLITS_SHIFT 8
+#define TULIP_ROUTE_SPLITS(r) ((r) >> TULIP_ROUTE_SPLITS_SHIFT)
+int tulip_gemm_route(int M, int N, int K, int a_trans, int b_trans, int epi, int accumulate, int splits);
 
 /* REDUCTIONS.  No kernel in this library funnels many workgroups into same-address atomics (on gfx950 a
  * chain of same-address device-scope fp32 atomics costs ~0.1-0.5 us per link).  Every cross-workgroup sum

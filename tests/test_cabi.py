@@ -46,6 +46,12 @@ def test_pure_host_entry_points():
     assert lib.tulip_gemm_effective_splits(32768, 128) == 128
     assert lib.tulip_gemm_effective_splits(100, 3) == 2
     assert lib.tulip_gemm_effective_splits(512, 1) == 1
+    # tulip_gemm_route: family | variant << 2 | flag bits | splits << 8 (the TULIP_ROUTE_* encoding of the header)
+    assert lib.tulip_gemm_route(4096, 3072, 64, 0, 0, 0, 0, 1) == _lib.ROUTE_FULL | 2 << 2 | 1 << 8            # whole 256-row tiles
+    assert lib.tulip_gemm_route(200, 104, 200, 1, 1, 3, 0, 3) == (_lib.ROUTE_TILE | _lib.ROUTE_A_TRANS | _lib.ROUTE_B_TRANS |
+                                                                  _lib.ROUTE_FOLD | 3 << 8)
+    assert lib.tulip_gemm_route(64, 96, 768, 0, 0, 7, _lib.GEMM_B_PACKED, 2) == _lib.ROUTE_STREAM | 1 << 2 | 2 << 8   # 384 per split, raw slabs
+    assert lib.tulip_gemm_route(64, 96, 36, 0, 0, 0, 0, 1) == -1                                                 # K % 8: TULIP_ERR_ARG
     assert lib.tulip_layernorm_bwd_partial_rows(32768, 96) == 512
     assert lib.tulip_layernorm_bwd_partial_rows(64, 1536) == 16
     assert lib.tulip_layernorm_bwd_partial_rows(16, 6144) == 0

@@ -85,6 +85,9 @@ REDUCE_REGIONS_MAX, WGRAD_GROUP_MAX, PACK_MAX = 48, 16, 64
 LR_GROUP_SHIFT, LR_GROUPS_MAX = 2, 64      # decay_mask64 bits 2-7: the block's learning-rate group (TULIP_LR_GROUP_SHIFT, csrc/common.h)
 GEMM_NO_TOUCH, GEMM_CHECKED, GEMM_NO_MID, GEMM_MID, WGRAD_SMALL_TILES, BLOCK_NO_WARM = 0x100, 0x200, 0x400, 0x800, 0x100, 8     # per-call flag bits (tulip_hip.h)
 GEMM_B_PACKED = 0x1000
+# tulip_gemm_route's bit field (TULIP_ROUTE_* of tulip_hip.h)
+ROUTE_TILE, ROUTE_FULL, ROUTE_MID, ROUTE_STREAM = range(4)
+ROUTE_DEEP, ROUTE_A_TRANS, ROUTE_B_TRANS, ROUTE_FOLD, ROUTE_SPLITS_SHIFT = 0x10, 0x20, 0x40, 0x80, 8
 ABI_VERSION = 6      # TULIP_ABI_VERSION of include/tulip_hip.h: the ctypes structs above mirror that layout
 
 # name -> argtypes (must mirror include/tulip_hip.h; tests/test_cabi.py cross-checks against the header)
@@ -136,6 +139,7 @@ SIGNATURES = {
     "tulip_wgrad_group_profiled": [P, I, P, L, I, P, P],
     "tulip_gemm_effective_splits": [I, I],
     "tulip_gemm_packed_supported": [I, I, I, I],
+    "tulip_gemm_route": [I, I, I, I, I, I, I, I],
     "tulip_cast_flat": [P, P, L, P],
     "tulip_cast_bf16_f32": [P, P, L, P],
     "tulip_tail_fwd": [P, P, P, P, P, I, I, I, I, P],

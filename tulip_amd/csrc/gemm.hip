@@ -350,6 +350,7 @@ template <int BM, bool A_T, bool B_T, int KSUB, bool FULL = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int bx, const int by, const int bz) {
     constexpr int FM = BM / 32;  // 16-row fragments per wave in M
     constexpr int FN = 3;
+    static_assert(!A_T || BM * 2 + 32 <= T_PITCH, "a k-slow tile row (T_PITCH bytes) holds at most 128 rows");
     using SA = Stage<BM, A_T, KSUB, FULL>;
     using SB = Stage<BN, B_T, KSUB, FULL>;
     constexpr int A_BYTES = KSUB * SA::SUB_BYTES, B_BYTES = KSUB * SB::SUB_BYTES;
@@ -1180,25 +1181,52 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const GemmArgs p, 
     }
 }
 
-template <bool A_T, bool B_T>
-int launch(const GemmArgs& p, int splits, hipStream_t stream) {
-    if constexpr (!A_T) {
+// ---- dispatch ---------------------------------------------------------------------------------------------------------
+// What one tulip_gemm_bf16 call launches, decided on the host from the shape and the flag word alone.  gemm_plan is the ONLY place
+// that decides: tulip_gemm_bf16 launches what it says (launch<> below switches on the plan and nothing else), tulip_gemm_route
+// reports it.
+struct GemmPlan {
+    int family;   // TULIP_ROUTE_TILE / _FULL / _MID / _STREAM
+    int bm;       // tile rows of the tile families: 64, 128, 256
+    int deep;     // 128-deep k stages (64-row tiles only)
+    int splits;   // K splits launched (gridDim.z)
+    int kchunk;   // K range per split
+    int fold;     // splitk_epilogue_kernel follows
+};
+static bool stream_shape_ok(int M, int N, int K, int kchunk);
+static int gemm_plan(int M, int N, int K, int a_trans, int b_trans, int epi, int flags, int splits, GemmPlan* pl) {
+    if (M <= 0 || N <= 0 || K <= 0) return TULIP_ERR_ARG;        // (nothing to launch: the entry point returns before it asks)
+    if ((K & 7) || (N & 7)) return TULIP_ERR_ARG;
+    if (a_trans && (M & 7)) return TULIP_ERR_ARG;
+    if (b_trans && (N & 7)) return TULIP_ERR_ARG;
+    if (splits < 1) splits = 1;
+    const int kchunk = (((K + splits - 1) / splits) + BK - 1) / BK * BK;     // K is cut in multiples of 32
+    splits = (K + kchunk - 1) / kchunk;
+    pl->kchunk = kchunk; pl->splits = splits;
+    pl->fold = splits > 1 && epi != TULIP_EPI_SPLIT_F32;
+    // (the fold kernel indexes its 8-column chunks with an int)
+    if (pl->fold && (int64_t)M * (N >> 3) >= (int64_t)1 << 31) return TULIP_ERR_ARG;
+    pl->bm = 0; pl->deep = 0;
+    if (flags & TULIP_GEMM_B_PACKED) {           // B: the fragment-major copy of the [N][K] matrix (gemm_stream_kernel)
+        if (a_trans || b_trans || !stream_shape_ok(M, N, K, kchunk)) return TULIP_ERR_ARG;
+        pl->family = TULIP_ROUTE_STREAM;
+        return TULIP_OK;
+    }
+    if (!a_trans && (flags & TULIP_GEMM_MID)) {
         // the 192 x 192 loader-wave kernel (whole 64-deep stages only): where the CALLER asks for it (TULIP_GEMM_MID) -- it wins on
         // narrow outputs over a deep K with the K split that fills the chip and loses elsewhere (profiles/r5_gemm_big.txt; a rule
         // of the launcher's own by tile count put the 32 768 x 96 x 192 skip Linear of the batch-8 step on it: 11 -> 17.6 us), so
         // the choice is the engine's (TulipEngine._gemm), not a heuristic down here
-        const int gx = (p.N + 191) / 192, gy = (p.M + 191) / 192;
-        const bool fits = p.kchunk % 64 == 0 && p.K % p.kchunk == 0 && p.N >= 96 && p.M >= 96 &&
-                          p.epi != TULIP_EPI_PIXSHUF2_F32 && p.epi != TULIP_EPI_UNSHUF2_BF16;
-        if (fits && p.mid == 2) {
-            hipLaunchKernelGGL((gemm_mid_kernel<B_T>), dim3(gx * gy * splits), dim3(512), 0, stream, p, gx, gy);
-            TULIP_CHECK_LAUNCH();
+        const bool fits = kchunk % 64 == 0 && K % kchunk == 0 && N >= 96 && M >= 96 &&
+                          epi != TULIP_EPI_PIXSHUF2_F32 && epi != TULIP_EPI_UNSHUF2_BF16;
+        if (fits) {
+            pl->family = TULIP_ROUTE_MID;
             return TULIP_OK;
         }
     }
     // BM=64 (with 128-deep k stages: 4 sub-tiles of loads in flight per thread) when BM=128 would leave
     // most of the 256 CUs idle -- the small-M / large-K GEMMs of the deep stages are load-latency bound
-    const int gn = (p.N + BN - 1) / BN;
+    const int gn = (N + BN - 1) / BN;
     // 64-row tiles unless the launch already has thousands of 128-row tiles: at B=8 every GEMM of this model
     // is latency-bound per workgroup, and twice as many half-size workgroups in flight measured 4 % faster
     // end to end
@@ -1206,15 +1234,40 @@ int launch(const GemmArgs& p, int splits, hipStream_t stream) {
     // 355 / 492 / 453, 4096x3072x768 441 / 461 / 529, 2048x6144x1536 519 / 555 / 704, 8192x2304x768 461 / 580 / 536, the N = 768
     // data gradients (K = 2304..6144) 287-312 / 261-297 / same: taller tiles only while at least two rounds of the chip remain,
     // 256 rows only for wide outputs (>= 32 column tiles).  Every GEMM of the batch-8 step stays on 64 rows.
-    const int t128 = ((p.M + 127) / 128) * gn * splits, t256 = ((p.M + 255) / 256) * gn * splits;
-    int bm = (t128 < TULIP_GEMM_MID_TILES || p.M <= 64) ? 64 : 128;
-    if (t256 >= TULIP_GEMM_MID_TILES && gn >= 32) bm = 256;
+    const int t128 = ((M + 127) / 128) * gn * splits, t256 = ((M + 255) / 256) * gn * splits;
+    int bm = (t128 < TULIP_GEMM_MID_TILES || M <= 64) ? 64 : 128;
+    // (256 rows never with a transposed A: a k-slow LDS tile holds 128 rows per k -- T_PITCH --, and the launcher used to send
+    // M >= 4096 weight-gradient shapes there all the same: every output wrong, tests/test_gemm_exact_gpu.py, t128-t?-m4096)
+    if (t256 >= TULIP_GEMM_MID_TILES && gn >= 32 && !a_trans) bm = 256;
+    pl->bm = bm;
+    const bool checked = (flags & TULIP_GEMM_CHECKED) != 0;
     if (bm == 64) {
-        dim3 grid(gn, (p.M + 63) / 64, splits);
         // 128-deep k stages (80-150 KB LDS, 1-2 workgroups/CU) pay while the grid is at most ~1.5 waves of the chip
-        const bool deep = (int)(grid.x * grid.y * grid.z) <= TULIP_GEMM_KSUB_GRID && p.kchunk >= 256;
-        const int bks = deep ? 128 : 32;
-        const bool full = !p.checked && !A_T && p.M % 64 == 0 && p.N % BN == 0 && p.kchunk % bks == 0 && p.K % p.kchunk == 0;
+        pl->deep = (int64_t)gn * ((M + 63) / 64) * splits <= TULIP_GEMM_KSUB_GRID && kchunk >= 256;
+    }
+    const int bks = pl->deep ? 128 : 32;
+    const bool full = !checked && !a_trans && M % bm == 0 && N % BN == 0 && kchunk % bks == 0 && K % kchunk == 0;
+    pl->family = full ? TULIP_ROUTE_FULL : TULIP_ROUTE_TILE;
+    return TULIP_OK;
+}
+
+template <bool A_T, bool B_T>
+int launch(const GemmArgs& p, const GemmPlan& pl, hipStream_t stream) {
+    const int splits = pl.splits;
+    if constexpr (!A_T) {
+        if (pl.family == TULIP_ROUTE_MID) {
+            const int gx = (p.N + 191) / 192, gy = (p.M + 191) / 192;
+            hipLaunchKernelGGL((gemm_mid_kernel<B_T>), dim3(gx * gy * splits), dim3(512), 0, stream, p, gx, gy);
+            TULIP_CHECK_LAUNCH();
+            return TULIP_OK;
+        }
+    }
+    if (pl.family != TULIP_ROUTE_TILE && (A_T || pl.family != TULIP_ROUTE_FULL)) return TULIP_ERR_ARG;   // (never: gemm_plan)
+    const int gn = (p.N + BN - 1) / BN, bm = pl.bm;
+    const bool full = pl.family == TULIP_ROUTE_FULL;
+    const dim3 grid(gn, (p.M + bm - 1) / bm, splits);
+    if (bm == 64) {
+        const bool deep = pl.deep != 0;
         if constexpr (!A_T) {
             if (full) {
                 if (deep) hipLaunchKernelGGL((gemm_kernel_full<64, B_T, 4>), grid, dim3(256), 0, stream, p);
@@ -1228,8 +1281,6 @@ int launch(const GemmArgs& p, int splits, hipStream_t stream) {
         else
             hipLaunchKernelGGL((gemm_kernel<64, A_T, B_T, 1>), grid, dim3(256), 0, stream, p);
     } else {
-        const bool full = !p.checked && !A_T && p.M % bm == 0 && p.N % BN == 0 && p.kchunk % 32 == 0 && p.K % p.kchunk == 0;
-        dim3 grid(gn, (p.M + bm - 1) / bm, splits);
         if constexpr (!A_T) {
             if (full) {
                 if (bm == 256) hipLaunchKernelGGL((gemm_kernel_full<256, B_T, 1>), grid, dim3(256), 0, stream, p);
@@ -1238,8 +1289,15 @@ int launch(const GemmArgs& p, int splits, hipStream_t stream) {
                 return TULIP_OK;
             }
         }
-        if (bm == 256) hipLaunchKernelGGL((gemm_kernel<256, A_T, B_T, 1>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_kernel<128, A_T, B_T, 1>), grid, dim3(256), 0, stream, p);
+        if constexpr (!A_T) {
+            if (bm == 256) {
+                hipLaunchKernelGGL((gemm_kernel<256, false, B_T, 1>), grid, dim3(256), 0, stream, p);
+                TULIP_CHECK_LAUNCH();
+                return TULIP_OK;
+            }
+        }
+        if (bm != 128) return TULIP_ERR_ARG;                                                               // (never: gemm_plan)
+        hipLaunchKernelGGL((gemm_kernel<128, A_T, B_T, 1>), grid, dim3(256), 0, stream, p);
     }
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
@@ -1261,29 +1319,37 @@ extern "C" int tulip_gemm_packed_supported(int M, int N, int K, int splits) {
     return stream_shape_ok(M, N, K, kchunk) ? 1 : 0;
 }
 
+extern "C" int tulip_gemm_route(int M, int N, int K, int a_trans, int b_trans, int epi, int accumulate, int splits) {
+    GemmPlan pl;
+    if (gemm_plan(M, N, K, a_trans, b_trans, epi, accumulate, splits, &pl) != TULIP_OK) return TULIP_ERR_ARG;
+    if (pl.splits >= 1 << 22) return TULIP_ERR_ARG;             // (K < 2^31 in 32-deep chunks: never)
+    const int variant = pl.family == TULIP_ROUTE_STREAM ? (pl.kchunk == 1536 ? 3 : pl.kchunk == 768 ? 2 : pl.kchunk == 384 ? 1 : 0)
+                        : pl.bm == 256 ? 2 : pl.bm == 128 ? 1 : 0;
+    return pl.family | variant << 2 | (pl.deep ? TULIP_ROUTE_DEEP : 0) | (a_trans ? TULIP_ROUTE_A_TRANS : 0) |
+           (b_trans ? TULIP_ROUTE_B_TRANS : 0) | (pl.fold ? TULIP_ROUTE_FOLD : 0) | pl.splits << TULIP_ROUTE_SPLITS_SHIFT;
+}
+
 extern "C" int tulip_gemm_bf16(const void* A, int lda, int a_trans, const void* B, int ldb, int b_trans, int M, int N,
                                int K, int epi, const float* bias, void* out, int ldo, void* out2, int ldo2,
                                const void* aux, int ldaux, const float* rowscale, int rows_per_sample, int accumulate,
                                int psH, int psW, int splits, void* workspace, int64_t workspace_bytes,
                                hipStream_t stream) {
     if (M <= 0 || N <= 0 || K <= 0) return TULIP_OK;
-    if ((K & 7) || (N & 7) || (lda & 7) || (ldb & 7)) return TULIP_ERR_ARG;
-    if (a_trans && (M & 7)) return TULIP_ERR_ARG;
-    if (b_trans && (N & 7)) return TULIP_ERR_ARG;
-    if (splits < 1) splits = 1;
-    const bool raw_split = epi == TULIP_EPI_SPLIT_F32;
-    if (splits > 1 && !raw_split) {
-        splits = effective_splits(K, splits);
-        if (splits > 1 && (!workspace || workspace_bytes < (int64_t)splits * M * N * 4)) return TULIP_ERR_ARG;
-    }
+    if ((lda & 7) || (ldb & 7)) return TULIP_ERR_ARG;
+    GemmPlan pl;
+    if (gemm_plan(M, N, K, a_trans, b_trans, epi, accumulate, splits, &pl) != TULIP_OK) return TULIP_ERR_ARG;
+    splits = pl.splits;
+    const bool fold = pl.fold != 0;
+    if (fold && (!workspace || workspace_bytes < (int64_t)splits * M * N * 4)) return TULIP_ERR_ARG;
+    // the row sums of the weight-gradient form come out of the GEMM kernel's own k loop: a folded launch has nowhere to put their
+    // partials (it used to return without ever writing out2) -- with splits > 1 they exist as TULIP_EPI_SPLIT_F32 slabs only
+    if (fold && a_trans && epi == TULIP_EPI_F32 && out2 && ldo2 <= 0) return TULIP_ERR_ARG;
     if ((epi == TULIP_EPI_RESID_F32 || epi == TULIP_EPI_GELU_BWD) && !aux) return TULIP_ERR_ARG;
     if (epi == TULIP_EPI_GELU_DUAL && !out2) return TULIP_ERR_ARG;
     GemmArgs p;
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.lda = lda; p.ldb = ldb;
     p.M = M; p.N = N; p.K = K;
-    int kchunk = (((K + splits - 1) / splits) + BK - 1) / BK * BK;
-    p.kchunk = kchunk;
-    splits = (K + kchunk - 1) / kchunk;
+    p.kchunk = pl.kchunk;
     p.epi = epi; p.bias = bias; p.out = out; p.ldo = ldo; p.out2 = out2; p.ldo2 = ldo2;
     p.aux = aux; p.ldaux = ldaux; p.rowscale = rowscale; p.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
     p.accumulate = accumulate & TULIP_GEMM_ACCUMULATE; p.psH = psH; p.psW = psW;
@@ -1293,28 +1359,25 @@ extern "C" int tulip_gemm_bf16(const void* A, int lda, int a_trans, const void* 
     p.vec_ok = epi == TULIP_EPI_PIXSHUF2_F32 ? ((ldo2 & 7) == 0 && ((uintptr_t)out2 & 15) == 0 && ((uintptr_t)out & 15) == 0)
              : epi == TULIP_EPI_UNSHUF2_BF16 ? ((ldo & 1) == 0 && ((uintptr_t)out & 3) == 0) : 0;
     GemmArgs q = p;  // what the GEMM kernel itself does
-    const bool fold = splits > 1 && !raw_split;
     if (fold) {
         q.epi = TULIP_EPI_SPLIT_F32; q.bias = nullptr; q.out = workspace; q.ldo = N; q.out2 = nullptr;
     }
     int rc;
-    if (accumulate & TULIP_GEMM_B_PACKED) {           // B: the fragment-major copy of the [N][K] matrix (gemm_stream_kernel)
-        if (a_trans || b_trans || !stream_shape_ok(M, N, K, kchunk)) return TULIP_ERR_ARG;
+    if (pl.family == TULIP_ROUTE_STREAM) {
         const dim3 grid(N / BN, M / 32, splits);
-        if (kchunk == 1536) hipLaunchKernelGGL((gemm_stream_kernel<48>), grid, dim3(256), 0, stream, q);
-        else if (kchunk == 768) hipLaunchKernelGGL((gemm_stream_kernel<24>), grid, dim3(256), 0, stream, q);
-        else if (kchunk == 384) hipLaunchKernelGGL((gemm_stream_kernel<12>), grid, dim3(256), 0, stream, q);
+        if (pl.kchunk == 1536) hipLaunchKernelGGL((gemm_stream_kernel<48>), grid, dim3(256), 0, stream, q);
+        else if (pl.kchunk == 768) hipLaunchKernelGGL((gemm_stream_kernel<24>), grid, dim3(256), 0, stream, q);
+        else if (pl.kchunk == 384) hipLaunchKernelGGL((gemm_stream_kernel<12>), grid, dim3(256), 0, stream, q);
         else hipLaunchKernelGGL((gemm_stream_kernel<3>), grid, dim3(256), 0, stream, q);
         hipError_t e__ = hipGetLastError();
         rc = e__ != hipSuccess ? -(1000 + (int)e__) : TULIP_OK;
     } else
-    if (!a_trans && !b_trans) rc = launch<false, false>(q, splits, stream);
-    else if (!a_trans && b_trans) rc = launch<false, true>(q, splits, stream);
-    else if (a_trans && b_trans) rc = launch<true, true>(q, splits, stream);
-    else rc = launch<true, false>(q, splits, stream);
+    if (!a_trans && !b_trans) rc = launch<false, false>(q, pl, stream);
+    else if (!a_trans && b_trans) rc = launch<false, true>(q, pl, stream);
+    else if (a_trans && b_trans) rc = launch<true, true>(q, pl, stream);
+    else rc = launch<true, false>(q, pl, stream);
     if (rc != TULIP_OK || !fold) return rc;
     const int64_t work = (int64_t)M * (N >> 3);
-    if (work >= (int64_t)1 << 31) return TULIP_ERR_ARG;
     const int grid = (int)std::min<int64_t>((work + 255) / 256, 2048);
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, stream, p, (const float*)workspace, splits);
     TULIP_CHECK_LAUNCH();

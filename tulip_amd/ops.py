@@ -32,6 +32,24 @@ def _chk(t: torch.Tensor, dtype, name: str):
                         f"{'cuda' if t.is_cuda else 'cpu'} contiguous={t.is_contiguous()}")
 
 
+def _gemm_flags(accumulate, touch, checked, mid, b_packed):
+    """the `accumulate` flag word of tulip_gemm_bf16"""
+    accumulate = int(bool(accumulate)) | (0 if touch else _lib.GEMM_NO_TOUCH) | (_lib.GEMM_CHECKED if checked else 0)
+    accumulate |= 0 if mid is None else (_lib.GEMM_MID if mid else _lib.GEMM_NO_MID)     # the 192 x 192 mid-size kernel: forced / never
+    accumulate |= _lib.GEMM_B_PACKED if b_packed else 0      # B = the fragment-major copy of the [N][K] matrix: the small-K form
+    return accumulate
+
+
+def gemm_route(M, N, K, *, a_trans=False, b_trans=False, epi=EPI_BF16, accumulate=False, splits=1, touch=True, checked=False,
+               mid=None, b_packed=False) -> int:
+    """tulip_gemm_route: the kernel gemm(...) launches for these arguments as the TULIP_ROUTE_* bit field of tulip_hip.h
+    (_lib.ROUTE_*); host code only, needs no GPU.  Raises where gemm(...) refuses the shape or the flags."""
+    r = _lib.load().tulip_gemm_route(M, N, K, int(a_trans), int(b_trans), epi, _gemm_flags(accumulate, touch, checked, mid, b_packed),
+                                     splits)
+    check(min(r, 0), "tulip_gemm_route")
+    return r
+
+
 def gemm(A, B, M, N, K, *, lda, ldb, a_trans=False, b_trans=False, epi=EPI_BF16, bias=None, out=None, ldo=None,
          out2=None, ldo2=0, aux=None, ldaux=0, rowscale=None, rows_per_sample=1, accumulate=False, psH=0, psW=0,
          splits=1, workspace=None, workspace_bytes=0, touch=True, checked=False, mid=None, b_packed=False):
@@ -39,9 +57,7 @@ def gemm(A, B, M, N, K, *, lda, ldb, a_trans=False, b_trans=False, epi=EPI_BF16,
     with an element offset (row strides passed as lda/ldb/ldo).  touch=False / checked=True: TULIP_GEMM_NO_TOUCH /
     TULIP_GEMM_CHECKED (measurement and bit-compare switches, per call)."""
     lib = _lib.load()
-    accumulate = int(bool(accumulate)) | (0 if touch else _lib.GEMM_NO_TOUCH) | (_lib.GEMM_CHECKED if checked else 0)
-    accumulate |= 0 if mid is None else (_lib.GEMM_MID if mid else _lib.GEMM_NO_MID)     # the 192 x 192 mid-size kernel: forced / never
-    accumulate |= _lib.GEMM_B_PACKED if b_packed else 0      # B = the fragment-major copy of the [N][K] matrix: the small-K form
+    accumulate = _gemm_flags(accumulate, touch, checked, mid, b_packed)
     rc = lib.tulip_gemm_bf16(_p(A), lda, int(a_trans), _p(B), ldb, int(b_trans), M, N, K, epi, _p(bias), _p(out),
                              ldo if ldo is not None else N, _p(out2), ldo2, _p(aux), ldaux, _p(rowscale),
                              rows_per_sample, int(accumulate), psH, psW, splits, _p(workspace), workspace_bytes,

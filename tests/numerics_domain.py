@@ -72,10 +72,21 @@ def _floor_log2(r64):
     return e.to(torch.int64) - 1
 
 
+def _pow2(k):
+    """2^k as float64 for an int64 tensor k in the normal range, assembled from its bits: exact on every device (torch.ldexp is
+    x * pow(2, k), and a device's float64 pow is not exact at every k -- a spacing one part in 2^53 off moves a tie)"""
+    assert bool(((k > -1023) & (k < 1024)).all())
+    return ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def _ulp_exp(r64, mant_bits, emin=-126):
+    e = torch.where(r64 == 0, torch.full_like(_floor_log2(r64), emin), _floor_log2(r64)).clamp(min=emin)
+    return e - mant_bits
+
+
 def ulp(r64, mant_bits, emin=-126):
     """spacing of a binary format with `mant_bits` stored mantissa bits (bf16: 7, fp32: 23) at |r|, subnormal range included"""
-    e = torch.where(r64 == 0, torch.full_like(_floor_log2(r64), emin), _floor_log2(r64)).clamp(min=emin)
-    return torch.ldexp(torch.ones_like(r64), (e - mant_bits).to(torch.int32))
+    return _pow2(_ulp_exp(r64, mant_bits, emin))
 
 
 def ulp_bf16(r64):
@@ -89,10 +100,10 @@ def ulp_f32(r64):
 def round_bf16(r64, truncate=False) -> torch.Tensor:
     """float64 -> the bf16 value (returned as bfloat16) nearest to it, ties to even, computed exactly in float64 (a cast through
     float32 would round twice); overflow to inf; truncate=True chops instead (the wrong conversion of the CPU tests)."""
-    u = ulp_bf16(r64)
-    q = r64 / u                                   # exact: a power-of-two scaling, |q| < 2^9
+    k = _ulp_exp(torch.where(torch.isfinite(r64), r64, torch.zeros_like(r64)), 7)
+    q = r64 * _pow2(-k)                           # exact: a power-of-two scaling, |q| < 2^9
     q = torch.trunc(q) if truncate else torch.round(q)     # torch.round: half to even
-    out = q * u
+    out = q * _pow2(k)
     out = torch.where(out.abs() >= 2.0 ** 128, torch.copysign(torch.full_like(out, math.inf), r64), out)
     out = torch.where(torch.isfinite(r64), out, r64)
     return out.to(torch.float32).to(torch.bfloat16)        # exact: `out` is a bf16 value

@@ -486,6 +486,19 @@ int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint16_t* p_bf1
                          const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
                          hipStream_t stream);
 
+/* Weight EMA: one update of an exponential moving average `shadow` of the parameters `p` (n floats, n % 4 == 0, both 16-byte
+ * aligned), torch_ema's ExponentialMovingAverage.update() as tulip_amd/ema.py restates it:
+ *   num_updates != NULL:  *num_updates += 1 (device word);  d = min(decay, (1 + *num_updates) / (10 + *num_updates))   [float64]
+ *   num_updates == NULL:  d = decay                                                                  (no warm-up, no counter)
+ *   omd = (float)(1.0 - d), written to omd_slot[0] (device)
+ *   per element, float32, three separately rounded operations, no fused multiply-add:  t = s - p;  t = omd * t;  s = s - t
+ * Two launches in stream order: the coefficient (one workgroup; the counter and omd live in device memory, so a captured graph
+ * replays the warm-up schedule with no host upload), then one streaming pass.  Bit-identical to the host definition.
+ * n <= 0: TULIP_OK, nothing launched.  n % 4 != 0, p / shadow / omd_slot NULL or misaligned, decay outside [0, 1] (NaN included):
+ * TULIP_ERR_ARG before any launch. */
+int tulip_ema_update(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
+                     hipStream_t stream);
+
 /* DropPath multipliers of one step (tulip.py:25-29; timm drop_path: keep a sample's residual branch with
  * probability keep, scale kept branches by 1/keep): scale[slot*B+b] = floor(keep[slot] + u)/keep[slot] with
  * u ~ U[0,1) from a counter-based generator keyed by (seed, *counter, index).  *counter is advanced by one:

@@ -305,6 +305,41 @@ __global__ __launch_bounds__(256) void adamw_kernel_blocks(float* __restrict__ p
     }
 }
 
+// ---------------------------------------------------------------- weight EMA (include/tulip_hip.h, "Weight EMA")
+// first launch, one workgroup: the step's coefficient in float64 -- the counter (optional) advances in device memory, so a captured
+// graph replays the warm-up schedule with no host upload -- rounded once to the float32 the streaming kernel multiplies with
+__global__ __launch_bounds__(64) void ema_coef_kernel(double decay, unsigned long long* num_updates, float* omd_slot) {
+    if (threadIdx.x != 0) return;
+    double d = decay;
+    if (num_updates) {
+        const unsigned long long n = *num_updates + 1ull;
+        *num_updates = n;
+        const double warm = (1.0 + (double)n) / (10.0 + (double)n);
+        d = warm < d ? warm : d;
+    }
+    omd_slot[0] = (float)(1.0 - d);
+}
+// second launch: s -= omd * (s - p), three separately rounded float32 operations (contraction off: the host definition,
+// tulip_amd/ema.py, has no fused multiply-add).  The shadow is read and written once per step and read by nothing else: the
+// streaming accesses of the optimizer state; p is loaded normally (the next AdamW reads it again).
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ s, int64_t n4,
+                                                         const float* __restrict__ omd_slot) {
+#pragma clang fp contract(off)
+    const float omd = omd_slot[0];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 pp = *(const float4*)(p + i * 4);
+        float4 ss = ld_state(s + i * 4);
+        float* S = (float*)&ss; const float* P = (const float*)&pp;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float t = S[k] - P[k];
+            t = omd * t;
+            S[k] = S[k] - t;
+        }
+        st_state(s + i * 4, ss);
+    }
+}
+
 // ---------------------------------------------------------------- DropPath draws (tulip.py:25-29, timm drop_path)
 // scale[slot][b] = floor(keep[slot] + u) / keep[slot], u ~ U[0,1) from a counter-based generator keyed by
 // (seed, step counter, index): one launch per step, graph-replayable (the counter lives in device memory).
@@ -576,6 +611,17 @@ extern "C" int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint
     else
         hipLaunchKernelGGL(adamw_kernel_blocks<false>, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
                            (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_ema_update(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
+                                hipStream_t stream) {
+    if (n <= 0) return TULIP_OK;
+    if ((n & 3) || !p || !shadow || !omd_slot || !(decay >= 0.0 && decay <= 1.0)) return TULIP_ERR_ARG;     // (a NaN decay fails the test)
+    if (((uintptr_t)p | (uintptr_t)shadow) & 15) return TULIP_ERR_ARG;                                      // float4 accesses
+    hipLaunchKernelGGL(ema_coef_kernel, dim3(1), dim3(64), 0, stream, decay, (unsigned long long*)num_updates, omd_slot);
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, shadow, n / 4, (const float*)omd_slot);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

@@ -440,6 +440,13 @@ def chamfer_sq(a, na, b, nb, is_f64, dist_a, dist_b, scratch, out):
                                        _p(out), _stream()), "tulip_chamfer_sq")
 
 
+def ema_update(p, shadow, n, decay, num_updates, omd_slot):
+    """tulip_ema_update: shadow -= omd * (shadow - p) over n floats; num_updates: int64 device word (None: no warm-up, no counter),
+    omd_slot: one float32 device word the launch pair hands the coefficient through."""
+    check(_lib.load().tulip_ema_update(_p(p), _p(shadow), int(n), float(decay), _p(num_updates), _p(omd_slot), _stream()),
+          "tulip_ema_update")
+
+
 def drop_path_scales(keep, scale, u_out, nslots, B, seed, counter):
     check(_lib.load().tulip_drop_path_scales(_p(keep), _p(scale), _p(u_out), nslots, B, int(seed) & (2 ** 64 - 1),
                                              _p(counter), _stream()), "tulip_drop_path_scales")

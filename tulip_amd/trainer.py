@@ -12,6 +12,8 @@ fp16).  Gradient accumulation (`accum_iter`, engine:90-97) runs the forward/back
 d(loss/accum_iter) accumulating into the flat gradient buffer; only the last micro-step of a window
 all-reduces (the sum of the per-micro-step all-reduces the reference issues) and applies AdamW.
 `train_one_epoch` is the reference's loop around it (per-iteration LR, non-finite-loss abort).
+`Trainer(ema_decay=...)` keeps an exponential moving average of the weights (tulip_amd.ema.ParamEMA): one more launch pair
+behind the last optimizer write of every optimizer step, inside the captured graphs.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch.distributed as dist
 
 from . import knobs, ops
 from .ddp import GradBucketer
+from .ema import ParamEMA, check_decay
 from .engine import ALIGN
 
 
@@ -60,7 +63,8 @@ class Trainer:
                  weight_decay: float = 0.01, device=None, use_graph: bool = True, process_group=None,
                  bucket_mb: float = 16.0, accum_iter: int = 1, track_grad_norm: bool = False,
                  force_segments: bool = False, bucket_adamw: Optional[bool] = None, grad_dtype: str = "fp32",
-                 attn_fp8: Optional[bool] = None, exchange: str = "allreduce", lr_scales=None):
+                 attn_fp8: Optional[bool] = None, exchange: str = "allreduce", lr_scales=None,
+                 ema_decay: Optional[float] = None, ema_use_num_updates: bool = True):
         """force_segments: run the N>1 step structure (graph segments cut at the bucket points, one all-reduce per
         bucket between replays) in a one-rank process group too -- how the RCCL path is exercised on a single GPU.
         bucket_adamw: None = environment default (TULIP_BUCKET_ADAMW, off).
@@ -75,7 +79,20 @@ class Trainer:
         recipe): {parameter name: float} -- names left out get 1.0, unknown names raise KeyError -- or a list of torch-style
         param groups carrying `lr_scale`.  Every AdamW site steps a tensor at fl32(lr * scale); at most 64 distinct scales
         (ValueError beyond); exchange="sharded" with scales other than 1.0 raises ValueError (that plan is optional and
-        unmeasured).  `step(lr=...)` keeps setting the unscaled rate."""
+        unmeasured).  `step(lr=...)` keeps setting the unscaled rate.
+        ema_decay: None (default): no average -- no buffer, no launch, the captured graphs and state_dict() are the ones without
+        it.  A float in [0, 1] (ValueError otherwise): `self.ema` is a tulip_amd.ema.ParamEMA over this model (ema_use_num_updates:
+        its warm-up, torch_ema's default) and its update runs once per OPTIMIZER step behind every optimizer write of that step,
+        inside the captured graphs.  One deviation from the reference's hook (engine_upsampling.py:94-95), which fires at every
+        iteration -- also at the accumulation micro-steps, where the parameters did not change: at accum_iter == 1 the two are
+        identical; for the per-iteration form leave ema_decay None and call a ParamEMA's update() yourself (train_one_epoch(ema=...)
+        does).  world > 1 needs no communication: every rank holds the same parameters and therefore the same average.
+        exchange="sharded" with ema_decay raises ValueError (the master is partial there; that plan is optional and unmeasured)."""
+        if ema_decay is not None:
+            ema_decay = check_decay(ema_decay)
+            if exchange == "sharded":
+                raise ValueError("exchange='sharded' with ema_decay is not supported (the fp32 master is partial between "
+                                 "gather_state() calls): use exchange='allreduce'")
         self.model = model
         device = device or torch.device("cuda", torch.cuda.current_device())
         self.device = device
@@ -205,6 +222,8 @@ class Trainer:
             self.eng.wgrad_ctas = self.eng.WGRAD_DDP_CTAS      # leave the CUs RCCL's channels sit on out of a round
         if lr_scales is not None:
             self.set_lr_scales(lr_scales)
+        # the weight average starts as a copy of the parameters this Trainer starts from (behind the broadcast above)
+        self.ema = ParamEMA(model, ema_decay, ema_use_num_updates, device) if ema_decay is not None else None
         W.refresh_shadow()
 
     # ------------------------------------------------------------------ per-parameter learning-rate scales
@@ -353,9 +372,19 @@ class Trainer:
             torch.cuda.current_stream().wait_stream(self._opt_stream)
             if not self.pack_at_step_start:
                 self.eng.params.refresh_transposes()
+            self._ema_update()                        # behind the wait: every bucket's optimizer launch is in front of it
         else:
             self.bucketer.wait_all()
             self._adamw()
+
+    def _ema_update(self):
+        """The weight average's update (Trainer(ema_decay=...)), at the one point of each step form that is behind EVERY optimizer
+        write of the step: the end of _adamw() -- the end-of-step launch in the eager step, in the one-GPU graph (run_backward has
+        joined the side queue, whose write-outs and fold launches take the fused steps, before it returns), in the "adamw" graph of
+        the segmented form and in the one graph with captured collectives -- and, with bucket_adamw, behind the wait for the
+        optimizer stream in _finish_buckets().  On the chain's own queue: never beside a fold launch."""
+        if self.ema is not None:
+            self.ema.update()
 
     def _adamw(self):
         W = self.eng.params
@@ -377,6 +406,7 @@ class Trainer:
                 W.refresh_transposes(late=True)
         elif not self.pack_at_step_start:
             W.refresh_transposes()
+        self._ema_update()
 
     # ------------------------------------------------------------------ checkpoint (misc.save_model / load_model keep
     # {'model', 'optimizer', 'epoch', ...}: this is the 'optimizer' entry of the fused AdamW)
@@ -384,20 +414,33 @@ class Trainer:
         W = self.eng.params
         self.gather_state()
         cut = lambda flat, n: flat[W.offset[n]:W.offset[n] + W.numel[n]].view(W.shape[n]).clone()
-        return {"step": self.t, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
-                "weight_decay": self.wd, "accum_iter": self.accum_iter, "lr_scales": dict(self.lr_scales),
-                "exp_avg": {n: cut(self.m, n) for n in W.names}, "exp_avg_sq": {n: cut(self.v, n) for n in W.names},
-                "grad": {n: cut(self.g, n) for n in W.names} if self.micro % self.accum_iter else None,
-                "drop_seed": int(self.eng._drop_seed), "drop_counter": int(self.eng._drop_counter.item()),
-                # the DropPath stream is seeded per rank (main_lidar_upsampling.py:155: args.seed + rank); a checkpoint is
-                # written by rank 0 and read by every rank, which re-derives its own seed from the saver's
-                "rank": dist.get_rank(self.process_group) if dist.is_initialized() else 0}
+        sd = {"step": self.t, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
+              "weight_decay": self.wd, "accum_iter": self.accum_iter, "lr_scales": dict(self.lr_scales),
+              "exp_avg": {n: cut(self.m, n) for n in W.names}, "exp_avg_sq": {n: cut(self.v, n) for n in W.names},
+              "grad": {n: cut(self.g, n) for n in W.names} if self.micro % self.accum_iter else None,
+              "drop_seed": int(self.eng._drop_seed), "drop_counter": int(self.eng._drop_counter.item()),
+              # the DropPath stream is seeded per rank (main_lidar_upsampling.py:155: args.seed + rank); a checkpoint is
+              # written by rank 0 and read by every rank, which re-derives its own seed from the saver's
+              "rank": dist.get_rank(self.process_group) if dist.is_initialized() else 0}
+        if self.ema is not None:                   # (no key without the average: the dictionary of a Trainer that keeps none is unchanged)
+            sd["ema"] = self.ema.state_dict()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         W = self.eng.params
         missing = [n for n in W.names if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
         if missing:
             raise KeyError(f"optimizer state lacks {len(missing)} parameters, e.g. {missing[:3]}")
+        if self.ema is not None:
+            if "ema" not in sd:
+                raise KeyError("this Trainer keeps a weight average (ema_decay) and the optimizer state has no 'ema' entry")
+            decay = self.ema.decay
+            self.ema.load_state_dict(sd["ema"])
+            if self.ema.decay != decay:
+                self._segments = None          # the decay is a launch argument baked into the captured graphs: re-capture
+        elif "ema" in sd:
+            sys.stderr.write("tulip_amd.Trainer: the optimizer state holds a weight average ('ema') and this Trainer keeps none "
+                             "(ema_decay=None): ignored\n")
         put = lambda flat, n, t: flat[W.offset[n]:W.offset[n] + W.numel[n]].copy_(t.reshape(-1).to(flat.dtype))
         for n in W.names:
             put(self.m, n, sd["exp_avg"][n])
@@ -771,6 +814,10 @@ class Trainer:
                 ops.adamw(scratch, scratch.clone(), scratch.clone(), scratch.clone(), None, 64, self.hyper,
                           torch.zeros(1, dtype=torch.uint8, device=self.device), lr_scale64=self._lr_table)
             ops.grad_norm(scratch, 64, self._norm_part, self.grad_norm)
+            if self.ema is not None:             # the average's kernels on scratch too: its shadow and counter stay as they are
+                ops.ema_update(scratch, scratch.clone(), 64, self.ema.decay,
+                               None if self.ema.counter is None else torch.zeros(1, dtype=torch.int64, device=self.device),
+                               torch.zeros(1, dtype=torch.float32, device=self.device))
             self.g.copy_(keep_g)
             self.eng._drop_counter.copy_(keep_c)
             del keep_g
@@ -812,14 +859,17 @@ class Trainer:
         return self.P.losses
 
 
-def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, log_every: int = 0) -> dict:
+def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, log_every: int = 0, ema=None) -> dict:
     """engine_upsampling.py:46-124 around the fused step: the learning rate is set from
     `data_iter_step / len(data_loader) + epoch` at the first micro-step of every accumulation window
     (engine:68-69), a non-finite loss prints both losses and exits with status 1 (engine:85-88), and
     the returned dict holds the epoch averages of `loss` and the last `lr` (engine:124).
     `args` needs lr, min_lr, warmup_epochs, epochs (lr_sched.py:9-21); batches are
     (low_res, high_res) tensors or the reference's ({'sample': ...}, {'sample': ...}) dicts.
-    Like the reference, the loss is read back every iteration (one host sync per step)."""
+    Like the reference, the loss is read back every iteration (one host sync per step).
+    ema: an object of the caller's with torch_ema's `update()` (a tulip_amd.ema.ParamEMA, say): called after EVERY trainer.step()
+    call, the reference's placement (engine:94-95).  The average a Trainer keeps itself (Trainer(ema_decay=...)) needs nothing
+    here: it is updated inside the step."""
     trainer.model.train(True)
     trainer.zero_grad()
     n = len(data_loader)
@@ -831,6 +881,8 @@ def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, l
             lo, hi = lo["sample"], hi["sample"]
         losses = trainer.step(lo.to(trainer.device, non_blocking=True), hi.to(trainer.device, non_blocking=True),
                               lr=lr).tolist()
+        if ema is not None:
+            ema.update()
         if not math.isfinite(losses[0]):
             print("Total Loss is {}, stopping training".format(losses[0]))
             print("Pixel Loss is {}, stopping training".format(losses[1]))

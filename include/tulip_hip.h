@@ -557,6 +557,19 @@ int tulip_window_attn_bwd_drop(const uint16_t* qkv, const uint16_t* dout, const 
 int tulip_grad_norm(const float* g, int64_t n, double* partials, const float* scale_dev, float scale, float* out,
                     hipStream_t stream);
 
+/* Gradient clipping by global norm (misc.py:299-300: torch.nn.utils.clip_grad_norm_(parameters, clip_grad) in front of
+ * optimizer.step()), folded into the gradient scale the AdamW launches behind it read (hyper[7] of tulip_adamw):
+ *   t = sum g[i]^2 (tulip_grad_norm's partition and fold order);  base = grad_scale[0];
+ *   norm = (float)(sqrt(t) * (double)base)     -- what tulip_grad_norm(g, n, partials, grad_scale, 1.0f, out) writes
+ *   c = max_norm_dev[0] / (norm + 1e-6f);  coef = c > 1.0f ? 1.0f : c    (fp32, one rounding per operation; a NaN norm gives
+ *                                                                          a NaN coef, an infinite norm gives 0)
+ *   out[0] = norm, out[1] = coef, grad_scale[0] = base * coef            (coef == 1.0f: grad_scale keeps its bits)
+ * Two launches in stream order, graph-capturable, nothing allocated.  g is only read and 16-byte aligned; partials: scratch of
+ * 1024 doubles.  TULIP_ERR_ARG before any launch: n <= 0, a NULL pointer, a misaligned g.  Host definition:
+ * tulip_amd/clip.py. */
+int tulip_grad_clip(const float* g, int64_t n, double* partials, float* grad_scale, const float* max_norm_dev, float* out,
+                    hipStream_t stream);
+
 /* Range-image input transforms in one pass (util/datasets.py): ScaleTensor :138-142, FilterInvalidPixels
  * :144-151, DownsampleTensor :117-125, DownsampleTensorWidth :127-135, LogTransform :68-70,
  * RandomRollRangeMap :96-107, composed as build_{durlar,kitti,carla}_upsampling_dataset do (:244-340).

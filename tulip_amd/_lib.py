@@ -191,6 +191,7 @@ SIGNATURES = {
     "tulip_window_attn_fwd_drop": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, ctypes.c_uint64, I, F, P],
     "tulip_window_attn_bwd_drop": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, ctypes.c_uint64, I, F, P],
     "tulip_grad_norm": [P, L, P, P, F, P, P],
+    "tulip_grad_clip": [P, L, P, P, P, P, P],
     "tulip_kitti_range_map": [P, L, I, I, F, F, F, F, F, P, P, P],
     "tulip_range_prep": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, I, P],
     "tulip_mc_aggregate": [P, I, L, F, P, P],

@@ -377,6 +377,31 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restri
         out[0] = (float)(sqrt(t) * (double)(scale_dev ? scale_dev[0] * scale : scale));
     }
 }
+// ---------------------------------------------------------------- gradient clipping by global norm (misc.py:299-300)
+// sumsq_final_kernel's fold, then torch.nn.utils.clip_grad_norm_'s coefficient folded into the gradient scale every AdamW launch
+// behind this one reads (hyper[7]): grad_scale[0] = base on entry, fl32(base * coef) on exit.  One rounding per operation
+// (contraction off); the comparison, not fminf: a NaN norm gives a NaN coefficient (torch.clamp), an infinite one gives 0.
+__global__ __launch_bounds__(256) void clip_final_kernel(const double* __restrict__ partials, int nblocks,
+                                                         float* __restrict__ grad_scale, const float* __restrict__ max_norm,
+                                                         float* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) s += partials[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double t = (red[0] + red[1]) + (red[2] + red[3]);
+        const float base = grad_scale[0];
+        const float norm = (float)(sqrt(t) * (double)base);
+        const float c = max_norm[0] / (norm + 1e-6f);
+        const float coef = (c > 1.0f) ? 1.0f : c;
+        out[0] = norm;
+        out[1] = coef;
+        grad_scale[0] = base * coef;
+    }
+}
 
 inline int grid_for(int64_t work, int cap = 256 * 8) {
     int64_t b = (work + 255) / 256;
@@ -641,6 +666,17 @@ extern "C" int tulip_grad_norm(const float* g, int64_t n, double* partials, cons
     const int nb = grid_for((n + 3) / 4, NORM_BLOCKS);
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, stream, g, partials, n);
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, partials, nb, scale_dev, scale, out);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_grad_clip(const float* g, int64_t n, double* partials, float* grad_scale, const float* max_norm_dev,
+                               float* out, hipStream_t stream) {
+    if (n <= 0 || !g || !partials || !grad_scale || !max_norm_dev || !out) return TULIP_ERR_ARG;
+    if ((uintptr_t)g & 15) return TULIP_ERR_ARG;                                                            // float4 loads
+    const int nb = grid_for((n + 3) / 4, NORM_BLOCKS);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, stream, g, partials, n);
+    hipLaunchKernelGGL(clip_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)partials, nb, grad_scale, max_norm_dev, out);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

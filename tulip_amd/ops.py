@@ -396,6 +396,13 @@ def grad_norm(g, n, partials, out, scale_dev=None, scale=1.0):
           "tulip_grad_norm")
 
 
+def grad_clip(g, n, partials, grad_scale, max_norm_dev, out):
+    """tulip_grad_clip: out[0] = the pre-clip norm sqrt(sum g^2) * grad_scale[0], out[1] = clip_grad_norm_'s coefficient for the
+    device float max_norm_dev, grad_scale[0] *= coefficient (tulip_amd/clip.py is the host definition).  g is only read."""
+    check(_lib.load().tulip_grad_clip(_p(g), n, _p(partials), _p(grad_scale), _p(max_norm_dev), _p(out), _stream()),
+          "tulip_grad_clip")
+
+
 def range_prep(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor,
                col_factor, row_phase, col_phase, scale, gate, min_range, max_range, log_transform, roll_shift):
     check(_lib.load().tulip_range_prep(_p(raw), raw_dtype, batch_stride, row_stride, col_stride, base_offset, _p(hi),

@@ -14,6 +14,8 @@ all-reduces (the sum of the per-micro-step all-reduces the reference issues) and
 `train_one_epoch` is the reference's loop around it (per-iteration LR, non-finite-loss abort).
 `Trainer(ema_decay=...)` keeps an exponential moving average of the weights (tulip_amd.ema.ParamEMA): one more launch pair
 behind the last optimizer write of every optimizer step, inside the captured graphs.
+`Trainer(clip_grad=...)` clips the gradients by their global norm (misc.py:299-300; tulip_amd/clip.py): the norm and the coefficient in
+front of one end-of-step AdamW, inside the captured graphs, the coefficient folded into the gradient scale that launch reads.
 """
 from __future__ import annotations
 
@@ -26,6 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import knobs, ops
+from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
 from .engine import ALIGN
@@ -64,7 +67,7 @@ class Trainer:
                  bucket_mb: float = 16.0, accum_iter: int = 1, track_grad_norm: bool = False,
                  force_segments: bool = False, bucket_adamw: Optional[bool] = None, grad_dtype: str = "fp32",
                  attn_fp8: Optional[bool] = None, exchange: str = "allreduce", lr_scales=None,
-                 ema_decay: Optional[float] = None, ema_use_num_updates: bool = True):
+                 ema_decay: Optional[float] = None, ema_use_num_updates: bool = True, clip_grad: Optional[float] = None):
         """force_segments: run the N>1 step structure (graph segments cut at the bucket points, one all-reduce per
         bucket between replays) in a one-rank process group too -- how the RCCL path is exercised on a single GPU.
         bucket_adamw: None = environment default (TULIP_BUCKET_ADAMW, off).
@@ -87,7 +90,20 @@ class Trainer:
         iteration -- also at the accumulation micro-steps, where the parameters did not change: at accum_iter == 1 the two are
         identical; for the per-iteration form leave ema_decay None and call a ParamEMA's update() yourself (train_one_epoch(ema=...)
         does).  world > 1 needs no communication: every rank holds the same parameters and therefore the same average.
-        exchange="sharded" with ema_decay raises ValueError (the master is partial there; that plan is optional and unmeasured)."""
+        exchange="sharded" with ema_decay raises ValueError (the master is partial there; that plan is optional and unmeasured).
+        clip_grad: None (default): no clipping -- no buffer, no launch, the captured graphs and state_dict() are the ones without
+        it.  A float >= 0 (ValueError for a negative value or NaN): misc.py:299-300, `clip_grad_norm_(parameters, clip_grad)` in
+        front of every optimizer step (tulip_amd/clip.py is the definition): the step takes the norm-first plan of track_grad_norm
+        -- no AdamW beside the backward, none per bucket, tulip_grad_clip in front of the one end-of-step launch, inside the
+        captured graphs -- and the coefficient goes into the gradient scale that launch reads (hyper[7]), not into the gradients.
+        `grad_norm` holds the pre-clip norm (what clip_grad_norm_ returns), `clip_coef` the coefficient, both device floats;
+        `trainer.clip_grad = x` between steps uploads one float (no re-capture).  exchange="sharded" with clip_grad raises
+        ValueError (every rank would need the norm over all shards before its first bucket steps)."""
+        if clip_grad is not None:
+            clip_grad = check_clip_grad(clip_grad)
+            if exchange == "sharded":
+                raise ValueError("exchange='sharded' with clip_grad is not supported (the per-bucket optimizer steps before the "
+                                 "global norm exists): use exchange='allreduce'")
         if ema_decay is not None:
             ema_decay = check_decay(ema_decay)
             if exchange == "sharded":
@@ -120,6 +136,14 @@ class Trainer:
         self.track_grad_norm = track_grad_norm
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=device)
         self._norm_part = torch.zeros(1024, dtype=torch.float64, device=device)
+        # misc.py:299-300 clip_grad_norm_: the norm first, like the read-out; [norm, coef] and the device float max_norm
+        self._clip_grad = clip_grad
+        self.clip_coef = None
+        if clip_grad is not None:
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
+            self.grad_norm, self.clip_coef = self._clip_out[0:1], self._clip_out[1:2]
+            self._clip_max = torch.full((1,), clip_grad, dtype=torch.float32, device=device)
+        norm_first = track_grad_norm or clip_grad is not None      # the optimizer waits for the norm over ALL gradients
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.bucketer = GradBucketer(W.groups, W.total, bucket_mb, process_group, force=force_segments)
         self.segmented = self.bucketer.active          # the step is cut at the bucket points
@@ -143,10 +167,10 @@ class Trainer:
             raise ValueError("exchange='sharded' with element dropout (drop_rate / attn_drop_rate > 0) is not supported: "
                              "use exchange='allreduce'")
         if self.exchange == "sharded":
-            if track_grad_norm or grad_dtype != "fp32" or self.accum_iter != 1:
+            if norm_first or grad_dtype != "fp32" or self.accum_iter != 1:
                 raise ValueError("exchange='sharded': fp32 gradients, no gradient-norm read-out, accum_iter == 1")
             bucket_adamw = True                      # the plan IS a per-bucket optimizer
-        self.bucket_adamw = self.segmented and not track_grad_norm and bool(bucket_adamw)
+        self.bucket_adamw = self.segmented and not norm_first and bool(bucket_adamw)
         self._opt_stream = torch.cuda.Stream(device=device) if self.bucket_adamw else None
         self._sharded = None                         # built at the first bucket (FlatParams.fp32_read is complete by then)
         # (FlatParams groups every parameter where it is last READ in the backward -- the skip Linears sit in their
@@ -176,8 +200,8 @@ class Trainer:
         # ... and where a weight-gradient workgroup holds a tensor's COMPLETE gradient tile (no token split: the deep stages, 90 %
         # of the parameters), the optimizer step is taken right there, in the write-out, beside the backward instead of behind it
         # (TULIP_FUSE_ADAMW=0: one AdamW launch over everything at the end of the step).  Captured steps on one GPU only: a
-        # gradient all-reduce, the gradient-norm read-out and accumulation need the gradients themselves.
-        self.fuse_adamw = (self.grad_overwrite and use_graph and not self.segmented and not track_grad_norm
+        # gradient all-reduce, the gradient-norm read-out, clipping and accumulation need the gradients themselves.
+        self.fuse_adamw = (self.grad_overwrite and use_graph and not self.segmented and not norm_first
                            and knobs.on("TULIP_FUSE_ADAMW", True))
         self._adam_mask = None
         self._adam_blocks = None
@@ -264,6 +288,22 @@ class Trainer:
         self._adam_mask, self._adam_blocks, self._adam_ctx, self._adam_fused = None, None, None, frozenset()
         self._adam_names, self._adam_sites = {}, {}
         self._segments = None
+
+    # ------------------------------------------------------------------ gradient clipping
+    @property
+    def clip_grad(self) -> Optional[float]:
+        return self._clip_grad
+
+    @clip_grad.setter
+    def clip_grad(self, max_norm) -> None:
+        """A new max_norm for the next optimizer step: one float uploaded on the current stream, the captured graphs stay (they
+        read it from device memory).  Switching clipping on or off changes the step plan: build another Trainer."""
+        if (max_norm is None) != (self._clip_grad is None):
+            raise ValueError("clip_grad cannot be switched on or off after construction (the step plan differs): "
+                             "build the Trainer with the clip_grad it is to run with")
+        if max_norm is not None:
+            self._clip_grad = check_clip_grad(max_norm)
+            self._clip_max.copy_(torch.full((1,), self._clip_grad, dtype=torch.float32))
 
     # ------------------------------------------------------------------ pieces
     def _set_hyper(self):
@@ -390,7 +430,11 @@ class Trainer:
         W = self.eng.params
         if self.gb is not None:                       # the summed bf16 gradients come back into the fp32 buffer
             ops.cast_bf16_f32(self.gb, self.g, W.total)
-        if self.track_grad_norm:
+        if self._clip_grad is not None:
+            # the pre-clip norm of DDP's mean gradient into grad_norm, the coefficient into clip_coef and into hyper[7]: the launch
+            # below steps on g * fl32(1/world * coef); the host uploads 1/world again at the next optimizer step (_set_hyper)
+            ops.grad_clip(self.g, W.total, self._norm_part, self.hyper[7:8], self._clip_max, self._clip_out)
+        elif self.track_grad_norm:
             # g holds the SUM over ranks here; hyper[7] = 1/world turns it into DDP's mean
             ops.grad_norm(self.g, W.total, self._norm_part, self.grad_norm, scale_dev=self.hyper[7:8])
         mask = self._adam_mask if self._adam_mask is not None else self._mask         # (bit 1: stepped beside the backward)
@@ -424,6 +468,8 @@ class Trainer:
               "rank": dist.get_rank(self.process_group) if dist.is_initialized() else 0}
         if self.ema is not None:                   # (no key without the average: the dictionary of a Trainer that keeps none is unchanged)
             sd["ema"] = self.ema.state_dict()
+        if self._clip_grad is not None:            # (likewise)
+            sd["clip_grad"] = self._clip_grad
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -441,6 +487,13 @@ class Trainer:
         elif "ema" in sd:
             sys.stderr.write("tulip_amd.Trainer: the optimizer state holds a weight average ('ema') and this Trainer keeps none "
                              "(ema_decay=None): ignored\n")
+        # clipping: the saved max_norm where both clip; a dictionary without the key (or from a run that did not clip) leaves the
+        # constructor's value, and a Trainer built without clipping stays without
+        if self._clip_grad is not None and sd.get("clip_grad") is not None:
+            self.clip_grad = sd["clip_grad"]
+        elif self._clip_grad is None and sd.get("clip_grad") is not None:
+            sys.stderr.write("tulip_amd.Trainer: the optimizer state was saved with gradient clipping ('clip_grad') and this Trainer "
+                             "clips nothing (clip_grad=None): ignored\n")
         put = lambda flat, n, t: flat[W.offset[n]:W.offset[n] + W.numel[n]].copy_(t.reshape(-1).to(flat.dtype))
         for n in W.names:
             put(self.m, n, sd["exp_avg"][n])
@@ -814,6 +867,9 @@ class Trainer:
                 ops.adamw(scratch, scratch.clone(), scratch.clone(), scratch.clone(), None, 64, self.hyper,
                           torch.zeros(1, dtype=torch.uint8, device=self.device), lr_scale64=self._lr_table)
             ops.grad_norm(scratch, 64, self._norm_part, self.grad_norm)
+            if self._clip_grad is not None:      # ... and the clip's pair, with a scale and an output of its own (hyper stays as uploaded)
+                ops.grad_clip(scratch, 64, self._norm_part, torch.ones(1, dtype=torch.float32, device=self.device), self._clip_max,
+                              torch.zeros(2, dtype=torch.float32, device=self.device))
             if self.ema is not None:             # the average's kernels on scratch too: its shadow and counter stay as they are
                 ops.ema_update(scratch, scratch.clone(), 64, self.ema.decay,
                                None if self.ema.counter is None else torch.zeros(1, dtype=torch.int64, device=self.device),

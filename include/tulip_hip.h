@@ -485,6 +485,14 @@ int tulip_adamw_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int6
 int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
                          const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
                          hipStream_t stream);
+/* tulip_adamw_s / tulip_adamw_blocks_s behind the non-finite guard (tulip_step_guard below): skip[0] != 0 (device word, one
+ * launch-uniform load) leaves p, m, v and p_bf16 unread and unwritten; with zero_grad the launch still clears the gradients the
+ * step would have cleared, and does nothing else.  skip[0] == 0 or skip == NULL: the bits of the _s entry. */
+int tulip_adamw_g(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, const float* hyper,
+                  const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad, const uint32_t* skip, hipStream_t stream);
+int tulip_adamw_blocks_g(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
+                         const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
+                         const uint32_t* skip, hipStream_t stream);
 
 /* Weight EMA: one update of an exponential moving average `shadow` of the parameters `p` (n floats, n % 4 == 0, both 16-byte
  * aligned), torch_ema's ExponentialMovingAverage.update() as tulip_amd/ema.py restates it:
@@ -498,6 +506,11 @@ int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint16_t* p_bf1
  * TULIP_ERR_ARG before any launch. */
 int tulip_ema_update(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
                      hipStream_t stream);
+/* ... behind the non-finite guard: skip[0] != 0 (device word) -- the counter does not advance, omd_slot and the shadow are not
+ * touched (the streaming kernel returns at entry; NOT omd = 0, which would turn a shadow of -0 over a parameter of +0 into +0).
+ * skip[0] == 0 or skip == NULL: the bits of tulip_ema_update. */
+int tulip_ema_update_g(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
+                       const uint32_t* skip, hipStream_t stream);
 
 /* DropPath multipliers of one step (tulip.py:25-29; timm drop_path: keep a sample's residual branch with
  * probability keep, scale kept branches by 1/keep): scale[slot*B+b] = floor(keep[slot] + u)/keep[slot] with
@@ -569,6 +582,20 @@ int tulip_grad_norm(const float* g, int64_t n, double* partials, const float* sc
  * tulip_amd/clip.py. */
 int tulip_grad_clip(const float* g, int64_t n, double* partials, float* grad_scale, const float* max_norm_dev, float* out,
                     hipStream_t stream);
+
+/* Non-finite guard (GradScaler.step()'s behaviour, misc.py:288-308: no optimizer step on Inf / NaN gradients), decided on the
+ * device from the norm tulip_grad_norm / tulip_grad_clip wrote (norm[0], float32).  state = {applied, skipped_total,
+ * skipped_consecutive}, three 64-bit device words; hyper = tulip_adamw's block.
+ *   norm is NaN or +-Inf:  skipped_total += 1, skipped_consecutive += 1, skip_flag[0] = 1; applied and hyper stay
+ *   otherwise:             applied += 1, skipped_consecutive = 0, skip_flag[0] = 0,
+ *                          hyper[5] = (float)(1 - beta1^applied), hyper[6] = (float)(1 - beta2^applied)
+ * with the power by binary exponentiation in float64 (r = 1, x = beta; while t: if t & 1: r *= x; t >>= 1; if t: x *= x), one
+ * rounding per multiplication: no transcendental function, bit-identical to the host definition (tulip_amd/guard.py).
+ * One workgroup, one working lane, plain stores; graph-capturable (a replayed graph advances the counters itself).  The launches
+ * behind it (tulip_adamw_g, tulip_adamw_blocks_g, tulip_ema_update_g) read skip_flag.  A NULL pointer or a state that is not
+ * 8-byte aligned: TULIP_ERR_ARG before any launch. */
+int tulip_step_guard(const float* norm, uint64_t* state, uint32_t* skip_flag, float* hyper, double beta1, double beta2,
+                     hipStream_t stream);
 
 /* Range-image input transforms in one pass (util/datasets.py): ScaleTensor :138-142, FilterInvalidPixels
  * :144-151, DownsampleTensor :117-125, DownsampleTensorWidth :127-135, LogTransform :68-70,

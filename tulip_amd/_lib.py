@@ -181,7 +181,12 @@ SIGNATURES = {
     "tulip_adamw_blocks_s": [P, P, P, P, P, P, I, P, P, P, I, P],
     "tulip_wgrad_group_adamw_s": [P, I, P, I, P, L, I, P, P, P],
     "tulip_reduce_rows_multi_adamw_s": [P, I, P, P, P],
+    # ... and behind the non-finite guard: a trailing-but-one device flag `skip` (tulip_step_guard writes it)
+    "tulip_adamw_g": [P, P, P, P, P, L, P, P, P, I, P, P],
+    "tulip_adamw_blocks_g": [P, P, P, P, P, P, I, P, P, P, I, P, P],
     "tulip_ema_update": [P, P, L, D, P, P, P],
+    "tulip_ema_update_g": [P, P, L, D, P, P, P, P],
+    "tulip_step_guard": [P, P, P, P, D, D, P],
     "tulip_drop_path_scales": [P, P, P, I, I, ctypes.c_uint64, P, P],
     "tulip_dropout_begin": [P, P, I, P],
     "tulip_dropout_mask": [P, ctypes.c_uint64, I, F, L, P, P],

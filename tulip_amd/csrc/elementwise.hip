@@ -258,14 +258,27 @@ __device__ __forceinline__ AdamwCoef adamw_coef_uniform(const float* __restrict_
     if constexpr (SC) return AdamwCoef{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (never read: every block has its own)
     else return adamw_coef(hyper, decay_on);
 }
-template <bool SC>
+// G: the non-finite guard (tulip_adamw_g, tulip_adamw_blocks_g): skip[0] != 0 -- one wave-uniform load at entry -- leaves p, m, v and the
+// bf16 copy unread and unwritten; with zero_grad the launch still clears what the step would have cleared.  G = false never reads
+// `skip`: the code of the entry points without a guard
+template <bool SC, bool G = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ pb, int64_t n, const float* __restrict__ hyper,
                                                     const uint8_t* __restrict__ mask64, const float* __restrict__ lr_scale,
-                                                    int zero_grad) {
-    [[maybe_unused]] const AdamwCoef cd = adamw_coef_uniform<SC>(hyper, true), cn = adamw_coef_uniform<SC>(hyper, false);
+                                                    int zero_grad, [[maybe_unused]] const uint32_t* __restrict__ skip) {
     const int64_t n4 = n >> 2;
+    if constexpr (G) {
+        if (skip[0] != 0u) {
+            if (!zero_grad) return;
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+                if ((mask64 ? mask64[i >> 4] : 1u) & 2u) continue;
+                *(float4*)(g + i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            return;
+        }
+    }
+    [[maybe_unused]] const AdamwCoef cd = adamw_coef_uniform<SC>(hyper, true), cn = adamw_coef_uniform<SC>(hyper, false);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const unsigned mk = mask64 ? mask64[i >> 4] : 1u;
         if (mk & 2u) continue;                       // this block's step was taken in a weight-gradient write-out
@@ -282,13 +295,23 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 
 // the same step over an explicit list of 64-element blocks (the few tensors left for the end of the step once everything else was
 // stepped where its gradient was completed): 16 lanes per block, nothing scanned
-template <bool SC>
+template <bool SC, bool G = false>
 __global__ __launch_bounds__(256) void adamw_kernel_blocks(float* __restrict__ p, float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v,
                                                            bf16_t* __restrict__ pb, const int32_t* __restrict__ blocks,
                                                            int nblocks, const float* __restrict__ hyper,
                                                            const uint8_t* __restrict__ mask64, const float* __restrict__ lr_scale,
-                                                           int zero_grad) {
+                                                           int zero_grad, [[maybe_unused]] const uint32_t* __restrict__ skip) {
+    if constexpr (G) {
+        if (skip[0] != 0u) {
+            if (!zero_grad) return;
+            for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < (int64_t)nblocks * 16; q += (int64_t)gridDim.x * 256) {
+                const int64_t i = (int64_t)blocks[q >> 4] * 16 + (q & 15);
+                *(float4*)(g + i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            return;
+        }
+    }
     [[maybe_unused]] const AdamwCoef cd = adamw_coef_uniform<SC>(hyper, true), cn = adamw_coef_uniform<SC>(hyper, false);
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < (int64_t)nblocks * 16; q += (int64_t)gridDim.x * 256) {
         const int blk = blocks[q >> 4];
@@ -308,8 +331,11 @@ __global__ __launch_bounds__(256) void adamw_kernel_blocks(float* __restrict__ p
 // ---------------------------------------------------------------- weight EMA (include/tulip_hip.h, "Weight EMA")
 // first launch, one workgroup: the step's coefficient in float64 -- the counter (optional) advances in device memory, so a captured
 // graph replays the warm-up schedule with no host upload -- rounded once to the float32 the streaming kernel multiplies with
-__global__ __launch_bounds__(64) void ema_coef_kernel(double decay, unsigned long long* num_updates, float* omd_slot) {
+// skip (tulip_ema_update_g; may be NULL): a set flag leaves the counter and the slot as they are
+__global__ __launch_bounds__(64) void ema_coef_kernel(double decay, unsigned long long* num_updates, float* omd_slot,
+                                                      const uint32_t* __restrict__ skip) {
     if (threadIdx.x != 0) return;
+    if (skip && skip[0] != 0u) return;
     double d = decay;
     if (num_updates) {
         const unsigned long long n = *num_updates + 1ull;
@@ -322,9 +348,13 @@ __global__ __launch_bounds__(64) void ema_coef_kernel(double decay, unsigned lon
 // second launch: s -= omd * (s - p), three separately rounded float32 operations (contraction off: the host definition,
 // tulip_amd/ema.py, has no fused multiply-add).  The shadow is read and written once per step and read by nothing else: the
 // streaming accesses of the optimizer state; p is loaded normally (the next AdamW reads it again).
+// G: returns at entry on the wave-uniform flag -- not "omd = 0", which turns a shadow of -0 over a parameter of +0 into +0.
+template <bool G>
 __global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ s, int64_t n4,
-                                                         const float* __restrict__ omd_slot) {
+                                                         const float* __restrict__ omd_slot,
+                                                         [[maybe_unused]] const uint32_t* __restrict__ skip) {
 #pragma clang fp contract(off)
+    if constexpr (G) { if (skip[0] != 0u) return; }
     const float omd = omd_slot[0];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const float4 pp = *(const float4*)(p + i * 4);
@@ -401,6 +431,40 @@ __global__ __launch_bounds__(256) void clip_final_kernel(const double* __restric
         out[1] = coef;
         grad_scale[0] = base * coef;
     }
+}
+
+// ---------------------------------------------------------------- non-finite step guard (include/tulip_hip.h, "Non-finite guard")
+// one working lane behind the norm: the decision, the three 64-bit counters and -- on a taken step -- the two bias corrections of
+// the APPLIED step count, 1 - beta^t with the power by binary exponentiation in float64, one rounding per multiplication
+// (contraction off; tulip_amd/guard.py is the definition).  Plain stores only.
+__device__ __forceinline__ float guard_bias_corr(double beta, unsigned long long t) {
+#pragma clang fp contract(off)
+    double r = 1.0, x = beta;
+    while (t) {
+        if (t & 1ull) r = r * x;
+        t >>= 1;
+        if (t) x = x * x;
+    }
+    return (float)(1.0 - r);
+}
+__global__ __launch_bounds__(64) void step_guard_kernel(const float* __restrict__ norm, unsigned long long* __restrict__ state,
+                                                        uint32_t* __restrict__ skip_flag, float* __restrict__ hyper,
+                                                        double beta1, double beta2) {
+    if (threadIdx.x != 0) return;
+    const uint32_t bits = __float_as_uint(norm[0]);
+    const bool bad = (bits & 0x7f800000u) == 0x7f800000u;           // NaN or +-Inf: every exponent bit set
+    if (bad) {
+        state[1] += 1ull;
+        state[2] += 1ull;
+        skip_flag[0] = 1u;
+        return;
+    }
+    const unsigned long long t = state[0] + 1ull;
+    state[0] = t;
+    state[2] = 0ull;
+    skip_flag[0] = 0u;
+    hyper[5] = guard_bias_corr(beta1, t);
+    hyper[6] = guard_bias_corr(beta2, t);
 }
 
 inline int grid_for(int64_t work, int cap = 256 * 8) {
@@ -611,10 +675,27 @@ extern "C" int tulip_adamw_s(float* p, float* g, float* m, float* v, uint16_t* p
     if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;         // the group index lives in the mask bytes
     if (lr_scale64)
         hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
-                           decay_mask64, lr_scale64, zero_grad);
+                           decay_mask64, lr_scale64, zero_grad, (const uint32_t*)nullptr);
     else
         hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
-                           decay_mask64, lr_scale64, zero_grad);
+                           decay_mask64, lr_scale64, zero_grad, (const uint32_t*)nullptr);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_adamw_g(float* p, float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, const float* hyper,
+                             const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad, const uint32_t* skip,
+                             hipStream_t stream) {
+    if (!skip) return tulip_adamw_s(p, g, m, v, p_bf16, n, hyper, decay_mask64, lr_scale64, zero_grad, stream);
+    if (n <= 0) return TULIP_OK;
+    if (n & 3) return TULIP_ERR_ARG;
+    if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;
+    if (lr_scale64)
+        hipLaunchKernelGGL((adamw_kernel<true, true>), dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
+                           decay_mask64, lr_scale64, zero_grad, skip);
+    else
+        hipLaunchKernelGGL((adamw_kernel<false, true>), dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, p_bf16, n, hyper,
+                           decay_mask64, lr_scale64, zero_grad, skip);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
@@ -632,21 +713,49 @@ extern "C" int tulip_adamw_blocks_s(float* p, float* g, float* m, float* v, uint
     if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;
     if (lr_scale64)
         hipLaunchKernelGGL(adamw_kernel_blocks<true>, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
-                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad);
+                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad, (const uint32_t*)nullptr);
     else
         hipLaunchKernelGGL(adamw_kernel_blocks<false>, dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m, v,
-                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad);
+                           (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad, (const uint32_t*)nullptr);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_adamw_blocks_g(float* p, float* g, float* m, float* v, uint16_t* p_bf16, const int32_t* blocks, int nblocks,
+                                    const float* hyper, const uint8_t* decay_mask64, const float* lr_scale64, int zero_grad,
+                                    const uint32_t* skip, hipStream_t stream) {
+    if (!skip)
+        return tulip_adamw_blocks_s(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad, stream);
+    if (nblocks <= 0) return TULIP_OK;
+    if (!p || !g || !m || !v || !blocks || !hyper) return TULIP_ERR_ARG;
+    if (lr_scale64 && !decay_mask64) return TULIP_ERR_ARG;
+    if (lr_scale64)
+        hipLaunchKernelGGL((adamw_kernel_blocks<true, true>), dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m,
+                           v, (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad, skip);
+    else
+        hipLaunchKernelGGL((adamw_kernel_blocks<false, true>), dim3(grid_for((int64_t)nblocks * 16)), dim3(256), 0, stream, p, g, m,
+                           v, (bf16_t*)p_bf16, blocks, nblocks, hyper, decay_mask64, lr_scale64, zero_grad, skip);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
 
 extern "C" int tulip_ema_update(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
                                 hipStream_t stream) {
+    return tulip_ema_update_g(p, shadow, n, decay, num_updates, omd_slot, nullptr, stream);
+}
+
+extern "C" int tulip_ema_update_g(const float* p, float* shadow, int64_t n, double decay, uint64_t* num_updates, float* omd_slot,
+                                  const uint32_t* skip, hipStream_t stream) {
     if (n <= 0) return TULIP_OK;
     if ((n & 3) || !p || !shadow || !omd_slot || !(decay >= 0.0 && decay <= 1.0)) return TULIP_ERR_ARG;     // (a NaN decay fails the test)
     if (((uintptr_t)p | (uintptr_t)shadow) & 15) return TULIP_ERR_ARG;                                      // float4 accesses
-    hipLaunchKernelGGL(ema_coef_kernel, dim3(1), dim3(64), 0, stream, decay, (unsigned long long*)num_updates, omd_slot);
-    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, shadow, n / 4, (const float*)omd_slot);
+    hipLaunchKernelGGL(ema_coef_kernel, dim3(1), dim3(64), 0, stream, decay, (unsigned long long*)num_updates, omd_slot, skip);
+    if (skip)
+        hipLaunchKernelGGL(ema_update_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, shadow, n / 4,
+                           (const float*)omd_slot, skip);
+    else
+        hipLaunchKernelGGL(ema_update_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, shadow, n / 4,
+                           (const float*)omd_slot, (const uint32_t*)nullptr);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
@@ -677,6 +786,16 @@ extern "C" int tulip_grad_clip(const float* g, int64_t n, double* partials, floa
     const int nb = grid_for((n + 3) / 4, NORM_BLOCKS);
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, stream, g, partials, n);
     hipLaunchKernelGGL(clip_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)partials, nb, grad_scale, max_norm_dev, out);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_step_guard(const float* norm, uint64_t* state, uint32_t* skip_flag, float* hyper, double beta1, double beta2,
+                                hipStream_t stream) {
+    if (!norm || !state || !skip_flag || !hyper) return TULIP_ERR_ARG;
+    if ((uintptr_t)state & 7) return TULIP_ERR_ARG;
+    hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(64), 0, stream, norm, (unsigned long long*)state, skip_flag, hyper, beta1,
+                       beta2);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

@@ -80,7 +80,10 @@ class ParamEMA:
         self.shadow = W.flat.clone()
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device) if use_num_updates else None
         self._omd = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._stash = None          # the parameters put aside by store()
+        # the non-finite guard's device flag (set by the Trainer(skip_nonfinite=True) that owns this average; None: no guard): an
+        # update behind a skipped optimizer step changes neither the counter nor the shadow (tulip_ema_update_g)
+        self.skip_flag = None
+        self._stash = None         # the parameters put aside by store()
         self._stored = False
         self._inside = False        # average_parameters() is not re-entrant
 
@@ -103,7 +106,7 @@ class ParamEMA:
     def update(self) -> None:
         from . import ops
         W = self._params()
-        ops.ema_update(W.flat, self.shadow, W.total, self.decay, self.counter, self._omd)
+        ops.ema_update(W.flat, self.shadow, W.total, self.decay, self.counter, self._omd, skip=self.skip_flag)
 
     # ------------------------------------------------------------------ evaluating with the averaged weights
     def store(self) -> None:

@@ -370,8 +370,13 @@ def l1_loss_bwd(pred, target, gscale_dev, gscale, dpred, n):
                                         _stream()), "tulip_l1_loss_bwd")
 
 
-def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None):
-    """lr_scale64: per-group learning-rate scales (pack_lr_groups; tulip_adamw_s) -- None: tulip_adamw."""
+def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None, skip=None):
+    """lr_scale64: per-group learning-rate scales (pack_lr_groups; tulip_adamw_s) -- None: tulip_adamw.
+    skip: the non-finite guard's device flag (step_guard; tulip_adamw_g) -- None: the entry points without it."""
+    if skip is not None:
+        check(_lib.load().tulip_adamw_g(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(hyper), _p(decay_mask64),
+                                        _p(lr_scale64), int(zero_grad), _p(skip), _stream()), "tulip_adamw_g")
+        return
     if lr_scale64 is not None:
         check(_lib.load().tulip_adamw_s(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(hyper), _p(decay_mask64),
                                         _p(lr_scale64), int(zero_grad), _stream()), "tulip_adamw_s")
@@ -380,8 +385,13 @@ def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_s
                                   int(zero_grad), _stream()), "tulip_adamw")
 
 
-def adamw_blocks(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None):
-    """tulip_adamw over the listed 64-float blocks only (blocks: int32 device tensor of block indices)."""
+def adamw_blocks(p, g, m, v, p_bf16, blocks, nblocks, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None, skip=None):
+    """tulip_adamw over the listed 64-float blocks only (blocks: int32 device tensor of block indices); skip: as in adamw."""
+    if skip is not None:
+        check(_lib.load().tulip_adamw_blocks_g(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(blocks), nblocks, _p(hyper),
+                                               _p(decay_mask64), _p(lr_scale64), int(zero_grad), _p(skip), _stream()),
+              "tulip_adamw_blocks_g")
+        return
     if lr_scale64 is not None:
         check(_lib.load().tulip_adamw_blocks_s(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(blocks), nblocks, _p(hyper),
                                                _p(decay_mask64), _p(lr_scale64), int(zero_grad), _stream()),
@@ -447,9 +457,22 @@ def chamfer_sq(a, na, b, nb, is_f64, dist_a, dist_b, scratch, out):
                                        _p(out), _stream()), "tulip_chamfer_sq")
 
 
-def ema_update(p, shadow, n, decay, num_updates, omd_slot):
+def step_guard(norm, state, skip_flag, hyper, beta1, beta2):
+    """tulip_step_guard: the non-finite guard's decision from the float32 device norm (tulip_amd/guard.py is the host definition).
+    state: int64[3] device words {applied, skipped_total, skipped_consecutive}; skip_flag: one uint32 device word (1 = skip);
+    hyper: the AdamW block, whose bias corrections [5], [6] a taken step rewrites for the applied count."""
+    check(_lib.load().tulip_step_guard(_p(norm), _p(state), _p(skip_flag), _p(hyper), float(beta1), float(beta2), _stream()),
+          "tulip_step_guard")
+
+
+def ema_update(p, shadow, n, decay, num_updates, omd_slot, skip=None):
     """tulip_ema_update: shadow -= omd * (shadow - p) over n floats; num_updates: int64 device word (None: no warm-up, no counter),
-    omd_slot: one float32 device word the launch pair hands the coefficient through."""
+    omd_slot: one float32 device word the launch pair hands the coefficient through.  skip: the non-finite guard's device flag
+    (tulip_ema_update_g: set, neither the counter nor the shadow changes) -- None: tulip_ema_update."""
+    if skip is not None:
+        check(_lib.load().tulip_ema_update_g(_p(p), _p(shadow), int(n), float(decay), _p(num_updates), _p(omd_slot), _p(skip),
+                                             _stream()), "tulip_ema_update_g")
+        return
     check(_lib.load().tulip_ema_update(_p(p), _p(shadow), int(n), float(decay), _p(num_updates), _p(omd_slot), _stream()),
           "tulip_ema_update")
 

@@ -16,9 +16,13 @@ all-reduces (the sum of the per-micro-step all-reduces the reference issues) and
 behind the last optimizer write of every optimizer step, inside the captured graphs.
 `Trainer(clip_grad=...)` clips the gradients by their global norm (misc.py:299-300; tulip_amd/clip.py): the norm and the coefficient in
 front of one end-of-step AdamW, inside the captured graphs, the coefficient folded into the gradient scale that launch reads.
+`Trainer(skip_nonfinite=True)` drops the optimizer step whose gradient norm is not finite (GradScaler.step(), misc.py:288-308;
+tulip_amd/guard.py): one single-workgroup launch behind the norm decides, AdamW and the EMA update behind it read its flag -- no host
+synchronisation, no re-capture, no extra collective.
 """
 from __future__ import annotations
 
+import gc
 import math
 import os
 import sys
@@ -31,6 +35,7 @@ from . import knobs, ops
 from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
+from .guard import check_skip_nonfinite
 from .engine import ALIGN
 
 
@@ -67,7 +72,8 @@ class Trainer:
                  bucket_mb: float = 16.0, accum_iter: int = 1, track_grad_norm: bool = False,
                  force_segments: bool = False, bucket_adamw: Optional[bool] = None, grad_dtype: str = "fp32",
                  attn_fp8: Optional[bool] = None, exchange: str = "allreduce", lr_scales=None,
-                 ema_decay: Optional[float] = None, ema_use_num_updates: bool = True, clip_grad: Optional[float] = None):
+                 ema_decay: Optional[float] = None, ema_use_num_updates: bool = True, clip_grad: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         """force_segments: run the N>1 step structure (graph segments cut at the bucket points, one all-reduce per
         bucket between replays) in a one-rank process group too -- how the RCCL path is exercised on a single GPU.
         bucket_adamw: None = environment default (TULIP_BUCKET_ADAMW, off).
@@ -98,7 +104,19 @@ class Trainer:
         captured graphs -- and the coefficient goes into the gradient scale that launch reads (hyper[7]), not into the gradients.
         `grad_norm` holds the pre-clip norm (what clip_grad_norm_ returns), `clip_coef` the coefficient, both device floats;
         `trainer.clip_grad = x` between steps uploads one float (no re-capture).  exchange="sharded" with clip_grad raises
-        ValueError (every rank would need the norm over all shards before its first bucket steps)."""
+        ValueError (every rank would need the norm over all shards before its first bucket steps).
+        skip_nonfinite: False (default): no guard -- no buffer, no launch, the captured graphs and state_dict() are the ones without
+        it.  True (ValueError for a non-bool): GradScaler.step()'s behaviour (misc.py:288-308; tulip_amd/guard.py is the definition):
+        the step takes the norm-first plan, computes the norm (also without track_grad_norm / clip_grad), and tulip_step_guard behind
+        it decides on the device: a NaN or infinite norm leaves parameters, bf16 copy, moments, EMA shadow and EMA counter as they
+        are (the gradients are still cleared where a taken step clears them) and counts the step as skipped; the optimizer's step
+        count and the bias corrections follow the APPLIED steps, on the device.  With world > 1 the norm is that of the all-reduced
+        gradient: every rank decides alike.  Read-outs: last_step_skipped (device uint32, no sync), skipped_steps, applied_steps,
+        consecutive_skips (ints, one host sync each).  exchange="sharded" with skip_nonfinite raises ValueError."""
+        skip_nonfinite = check_skip_nonfinite(skip_nonfinite)
+        if skip_nonfinite and exchange == "sharded":
+            raise ValueError("exchange='sharded' with skip_nonfinite is not supported (the per-bucket optimizer steps before the "
+                             "global norm exists): use exchange='allreduce'")
         if clip_grad is not None:
             clip_grad = check_clip_grad(clip_grad)
             if exchange == "sharded":
@@ -143,7 +161,14 @@ class Trainer:
             self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
             self.grad_norm, self.clip_coef = self._clip_out[0:1], self._clip_out[1:2]
             self._clip_max = torch.full((1,), clip_grad, dtype=torch.float32, device=device)
-        norm_first = track_grad_norm or clip_grad is not None      # the optimizer waits for the norm over ALL gradients
+        # GradScaler.step() (misc.py:288-308): the device words of the non-finite guard -- {applied, skipped_total,
+        # skipped_consecutive} and the flag the launches behind the decision read
+        self.skip_nonfinite = skip_nonfinite
+        self._guard_state = self._skip_flag = None
+        if skip_nonfinite:
+            self._guard_state = torch.zeros(3, dtype=torch.int64, device=device)
+            self._skip_flag = torch.zeros(1, dtype=torch.int32, device=device).view(torch.uint32)
+        norm_first = track_grad_norm or clip_grad is not None or skip_nonfinite      # the optimizer waits for the norm over ALL gradients
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.bucketer = GradBucketer(W.groups, W.total, bucket_mb, process_group, force=force_segments)
         self.segmented = self.bucketer.active          # the step is cut at the bucket points
@@ -248,6 +273,8 @@ class Trainer:
             self.set_lr_scales(lr_scales)
         # the weight average starts as a copy of the parameters this Trainer starts from (behind the broadcast above)
         self.ema = ParamEMA(model, ema_decay, ema_use_num_updates, device) if ema_decay is not None else None
+        if self.ema is not None:
+            self.ema.skip_flag = self._skip_flag        # (None without the guard)
         W.refresh_shadow()
 
     # ------------------------------------------------------------------ per-parameter learning-rate scales
@@ -304,6 +331,44 @@ class Trainer:
         if max_norm is not None:
             self._clip_grad = check_clip_grad(max_norm)
             self._clip_max.copy_(torch.full((1,), self._clip_grad, dtype=torch.float32))
+
+    # ------------------------------------------------------------------ non-finite guard
+    def _guard_word(self, k: int) -> int:
+        if self._guard_state is None:
+            raise AttributeError("this Trainer has no non-finite guard: build it with skip_nonfinite=True")
+        return int(self._guard_state[k].item())
+
+    @property
+    def last_step_skipped(self) -> torch.Tensor:
+        """The flag of the last optimizer step (device uint32[1], 1 = skipped; no host sync)."""
+        if self._skip_flag is None:
+            raise AttributeError("this Trainer has no non-finite guard: build it with skip_nonfinite=True")
+        return self._skip_flag
+
+    @property
+    def applied_steps(self) -> int:
+        """Optimizer steps actually taken (one host sync): the optimizer's step count."""
+        return self._guard_word(0)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Optimizer steps skipped in all (one host sync)."""
+        return self._guard_word(1)
+
+    @property
+    def consecutive_skips(self) -> int:
+        """The current run of skipped optimizer steps (one host sync); 0 after a taken step."""
+        return self._guard_word(2)
+
+    def _set_guard_counters(self, applied: int, skipped: int = 0, consecutive: int = 0) -> None:
+        self._guard_state.copy_(torch.tensor([int(applied), int(skipped), int(consecutive)], dtype=torch.int64))
+        self.t = int(applied)
+
+    def _set_betas(self, betas) -> None:
+        betas = tuple(betas)
+        if self.skip_nonfinite and betas != tuple(self.betas):
+            self._segments = None          # the guard's betas are launch arguments baked into the captured graphs: re-capture
+        self.betas = betas
 
     # ------------------------------------------------------------------ pieces
     def _set_hyper(self):
@@ -434,17 +499,22 @@ class Trainer:
             # the pre-clip norm of DDP's mean gradient into grad_norm, the coefficient into clip_coef and into hyper[7]: the launch
             # below steps on g * fl32(1/world * coef); the host uploads 1/world again at the next optimizer step (_set_hyper)
             ops.grad_clip(self.g, W.total, self._norm_part, self.hyper[7:8], self._clip_max, self._clip_out)
-        elif self.track_grad_norm:
+        elif self.track_grad_norm or self.skip_nonfinite:
             # g holds the SUM over ranks here; hyper[7] = 1/world turns it into DDP's mean
             ops.grad_norm(self.g, W.total, self._norm_part, self.grad_norm, scale_dev=self.hyper[7:8])
+        if self.skip_nonfinite:
+            # the decision, from the norm just written (with world > 1: of the all-reduced gradient, the same on every rank): the
+            # counters, the flag and -- on a taken step -- the bias corrections of the applied count over the host's upload.  The
+            # AdamW launch and the average's update behind it read the flag
+            ops.step_guard(self.grad_norm, self._guard_state, self._skip_flag, self.hyper, self.betas[0], self.betas[1])
         mask = self._adam_mask if self._adam_mask is not None else self._mask         # (bit 1: stepped beside the backward)
         if self._adam_blocks is not None:
             # most tensors were stepped where their gradient was completed: the few blocks left, by index (nothing scanned)
             ops.adamw_blocks(W.flat, self.g, self.m, self.v, W.shadow, self._adam_blocks, self._adam_blocks.numel(), self.hyper,
-                             mask, zero_grad=not self.grad_overwrite, lr_scale64=self._lr_table)
+                             mask, zero_grad=not self.grad_overwrite, lr_scale64=self._lr_table, skip=self._skip_flag)
         else:
             ops.adamw(W.flat, self.g, self.m, self.v, W.shadow, W.total, self.hyper, mask, zero_grad=not self.grad_overwrite,
-                      lr_scale64=self._lr_table)
+                      lr_scale64=self._lr_table, skip=self._skip_flag)
         if self._pack_at_end:
             if W.pk_late:
                 W.refresh_transposes(late=True)
@@ -458,7 +528,10 @@ class Trainer:
         W = self.eng.params
         self.gather_state()
         cut = lambda flat, n: flat[W.offset[n]:W.offset[n] + W.numel[n]].view(W.shape[n]).clone()
-        sd = {"step": self.t, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
+        applied = self.t
+        if self.skip_nonfinite:                    # the optimizer's step count is the APPLIED count, which only the device knows
+            applied, skipped, consecutive = (int(x) for x in self._guard_state.tolist())
+        sd = {"step": applied, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
               "weight_decay": self.wd, "accum_iter": self.accum_iter, "lr_scales": dict(self.lr_scales),
               "exp_avg": {n: cut(self.m, n) for n in W.names}, "exp_avg_sq": {n: cut(self.v, n) for n in W.names},
               "grad": {n: cut(self.g, n) for n in W.names} if self.micro % self.accum_iter else None,
@@ -470,6 +543,8 @@ class Trainer:
             sd["ema"] = self.ema.state_dict()
         if self._clip_grad is not None:            # (likewise)
             sd["clip_grad"] = self._clip_grad
+        if self.skip_nonfinite:                    # (likewise)
+            sd["guard"] = {"applied": applied, "skipped": skipped, "consecutive": consecutive}
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -503,7 +578,15 @@ class Trainer:
             for n in W.names:
                 put(self.g, n, sd["grad"][n])
         self.t, self.micro, self.lr = int(sd["step"]), int(sd["micro"]), float(sd["lr"])
-        self.betas, self.eps, self.wd = tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
+        self._set_betas(sd["betas"])
+        self.eps, self.wd = float(sd["eps"]), float(sd["weight_decay"])
+        if self.skip_nonfinite:
+            # the device counters; a dictionary without the entry (an unguarded run's): every step so far was applied
+            gd = sd.get("guard") or {"applied": int(sd["step"]), "skipped": 0, "consecutive": 0}
+            self._set_guard_counters(gd["applied"], gd["skipped"], gd["consecutive"])
+        elif sd.get("guard") is not None:
+            sys.stderr.write("tulip_amd.Trainer: the optimizer state was saved with the non-finite guard ('guard') and this Trainer "
+                             "has none (skip_nonfinite=False): the skip counters are ignored\n")
         saved = sd.get("lr_scales")                # (a dictionary saved before the scales existed: all ones)
         if (saved if saved is not None else {n: 1.0 for n in W.names}) != self.lr_scales:
             self.set_lr_scales(saved)
@@ -641,7 +724,10 @@ class Trainer:
             raise ValueError(f"cannot import: {len(W.names) - len(seen)} parameters missing, steps {sorted(steps)}, decays {sorted(wds)}")
         g0 = optimizer.param_groups[0]
         self.set_lr_scales(scales)
-        self.t, self.lr, self.betas, self.eps = steps.pop(), base_lr, tuple(g0["betas"]), float(g0["eps"])
+        self.t, self.lr, self.eps = steps.pop(), base_lr, float(g0["eps"])
+        self._set_betas(g0["betas"])
+        if self.skip_nonfinite:                    # the imported step count is the applied count; the skip counters keep theirs
+            self._set_guard_counters(self.t, self.skipped_steps, self.consecutive_skips)
         if wds:
             self.wd = wds.pop()
         self.g.zero_()
@@ -654,6 +740,7 @@ class Trainer:
         lr = lr * lr_scale (what the reference's schedule leaves there, util/lr_sched.py:16-20) and, where the scale is not 1.0
         or the group already has the key, `lr_scale`; a group whose parameters do not share one scale raises ValueError."""
         W, by_ptr = self.eng.params, self._param_names_by_ptr()
+        step_count = self.applied_steps if self.skip_nonfinite else self.t
         for grp in optimizer.param_groups:
             sc = {self.lr_scales[by_ptr[p.data_ptr()]] for p in grp["params"]}
             if len(sc) > 1:
@@ -666,7 +753,7 @@ class Trainer:
             for p in grp["params"]:
                 n = by_ptr[p.data_ptr()]
                 sl = slice(W.offset[n], W.offset[n] + W.numel[n])
-                optimizer.state[p] = {"step": torch.tensor(float(self.t)), "exp_avg": self.m[sl].view(W.shape[n]).clone(),
+                optimizer.state[p] = {"step": torch.tensor(float(step_count)), "exp_avg": self.m[sl].view(W.shape[n]).clone(),
                                       "exp_avg_sq": self.v[sl].view(W.shape[n]).clone()}
 
     # ------------------------------------------------------------------ graph capture
@@ -870,16 +957,29 @@ class Trainer:
             if self._clip_grad is not None:      # ... and the clip's pair, with a scale and an output of its own (hyper stays as uploaded)
                 ops.grad_clip(scratch, 64, self._norm_part, torch.ones(1, dtype=torch.float32, device=self.device), self._clip_max,
                               torch.zeros(2, dtype=torch.float32, device=self.device))
+            flag = None
+            if self.skip_nonfinite:              # the guard's launch and the gated AdamW forms, on counters, a flag and a hyper block of their own
+                flag = torch.zeros(1, dtype=torch.int32, device=self.device).view(torch.uint32)
+                ops.step_guard(torch.ones(1, dtype=torch.float32, device=self.device),
+                               torch.zeros(3, dtype=torch.int64, device=self.device), flag, self.hyper.clone(), *self.betas)
+                ops.adamw(scratch, scratch.clone(), scratch.clone(), scratch.clone(), None, 64, self.hyper,
+                          None if self._lr_table is None else torch.zeros(1, dtype=torch.uint8, device=self.device),
+                          lr_scale64=self._lr_table, skip=flag)
             if self.ema is not None:             # the average's kernels on scratch too: its shadow and counter stay as they are
                 ops.ema_update(scratch, scratch.clone(), 64, self.ema.decay,
                                None if self.ema.counter is None else torch.zeros(1, dtype=torch.int64, device=self.device),
-                               torch.zeros(1, dtype=torch.float32, device=self.device))
+                               torch.zeros(1, dtype=torch.float32, device=self.device), skip=flag)
             self.g.copy_(keep_g)
             self.eng._drop_counter.copy_(keep_c)
             del keep_g
             torch.cuda.synchronize()
             self._pack_epoch = self.eng.params.pack_epoch
             self._seg_drop = self.eng.dropout_state()
+            # no cyclic garbage collection inside the captures: a dead reference cycle that holds a CUDAGraph of an earlier Trainer
+            # (a test's saved exception info, a local class) is collected wherever the collector happens to run, and on ROCm
+            # ~CUDAGraph synchronises the device -- not permitted while this thread captures: the process aborts
+            gc_on = gc.isenabled()
+            gc.disable()
             try:
                 self._segments = {True: self._capture(True)}
                 if self.accum_iter > 1:
@@ -888,6 +988,9 @@ class Trainer:
                 self._segments = None
                 self.P.reset_exchange()       # a launch sequence cut short may have left an arrival ticket half-counted
                 raise
+            finally:
+                if gc_on:
+                    gc.enable()
         for graph, tag in self._segments[update]:
             self.progress = (self.t, f"segment:{tag}")
             if tag == "adamw":
@@ -925,11 +1028,20 @@ def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, l
     Like the reference, the loss is read back every iteration (one host sync per step).
     ema: an object of the caller's with torch_ema's `update()` (a tulip_amd.ema.ParamEMA, say): called after EVERY trainer.step()
     call, the reference's placement (engine:94-95).  The average a Trainer keeps itself (Trainer(ema_decay=...)) needs nothing
-    here: it is updated inside the step."""
+    here: it is updated inside the step.
+    A guarded trainer (Trainer(skip_nonfinite=True)): the skip flag of every optimizer step is read along with the loss (the same
+    host sync).  A skipped step prints one line, its loss (and those of its accumulation window) stays out of the epoch average,
+    and the loop exits with status 1 only when `getattr(args, "max_skipped_steps", 10)` optimizer steps in a row were skipped.  A
+    non-finite loss of a step that was NOT skipped (a NaN target pixel: NaN loss, zero gradient there) still exits, as in the
+    reference; inside an accumulation window that verdict waits for the window's optimizer step."""
     trainer.model.train(True)
     trainer.zero_grad()
     n = len(data_loader)
     tot, cnt, lr = 0.0, 0, trainer.lr
+    guarded = bool(getattr(trainer, "skip_nonfinite", False))
+    max_skips = int(getattr(args, "max_skipped_steps", 10))
+    window = []                  # guarded: the (reduced) losses of the open accumulation window and its first non-finite pair
+    window_bad = None
     for it, (lo, hi) in enumerate(data_loader):
         if it % trainer.accum_iter == 0:
             lr = cosine_lr(it / n + epoch, args.lr, args.min_lr, args.warmup_epochs, args.epochs)
@@ -939,7 +1051,25 @@ def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, l
                               lr=lr).tolist()
         if ema is not None:
             ema.update()
-        if not math.isfinite(losses[0]):
+        if guarded:
+            if not math.isfinite(losses[0]) and window_bad is None:
+                window_bad = losses
+            if trainer.micro % trainer.accum_iter != 0:
+                losses = [0.0, 0.0] if not math.isfinite(losses[0]) else losses      # (the window's verdict is pending)
+            elif int(trainer.last_step_skipped.item()):
+                run = trainer.consecutive_skips
+                print(f"Epoch: [{epoch}]  [{it + 1}/{n}]  non-finite gradient norm: optimizer step skipped "
+                      f"({run} in a row, {trainer.skipped_steps} in all; loss {(window_bad or losses)[0]})")
+                if run >= max_skips:
+                    print("{} optimizer steps skipped in a row, stopping training".format(run))
+                    sys.exit(1)
+                window, window_bad = [], None
+                continue
+            elif window_bad is not None:
+                print("Total Loss is {}, stopping training".format(window_bad[0]))
+                print("Pixel Loss is {}, stopping training".format(window_bad[1]))
+                sys.exit(1)
+        elif not math.isfinite(losses[0]):
             print("Total Loss is {}, stopping training".format(losses[0]))
             print("Pixel Loss is {}, stopping training".format(losses[1]))
             sys.exit(1)
@@ -948,7 +1078,14 @@ def train_one_epoch(trainer: Trainer, data_loader: Iterable, epoch: int, args, l
             red = torch.tensor(losses, dtype=torch.float32, device=trainer.device)
             dist.all_reduce(red, group=trainer.process_group)
             losses = (red / trainer.world).tolist()
-        tot, cnt = tot + losses[0], cnt + 1
+        if guarded:
+            # a window's losses enter the average when its optimizer step was taken
+            window.append(losses[0])
+            if trainer.micro % trainer.accum_iter == 0:
+                tot, cnt = tot + sum(window), cnt + len(window)
+                window = []
+        else:
+            tot, cnt = tot + losses[0], cnt + 1
         if log_every and (it + 1) % log_every == 0:
             print(f"Epoch: [{epoch}]  [{it + 1}/{n}]  lr: {lr:.6f}  loss: {losses[0]:.4f}")
     return {"loss": tot / max(cnt, 1), "lr": lr}

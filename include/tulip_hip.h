@@ -464,6 +464,40 @@ int tulip_l1_loss_fwd(const float* pred, const float* target, float* partials, f
 int tulip_l1_loss_bwd(const float* pred, const float* target, const float* gscale_dev, float gscale, float* dpred,
                       int64_t n, hipStream_t stream);
 
+/* The selectable training loss, TULIP(loss="l1" | "l2" | "berhu") (host definition: tulip_amd/loss.py).  With d = pred - target
+ * over n elements:
+ *   TULIP_LOSS_L2     loss = mean d^2,  d(loss)/d(pred) = 2 d / n
+ *   TULIP_LOSS_BERHU  C = 0.2f * max|d| (fp32, constant under differentiation: util/evaluation.py:177-180, inverse_huber_loss);
+ *                     value |d| where |d| < C, (d^2 + C^2) / (2 C) elsewhere; loss = the mean of the values; gradient sign(d) / n
+ *                     where |d| < C, d / (C n) elsewhere.  C == 0 (pred == target everywhere, 0/0 in the reference): loss and
+ *                     gradient are 0.  A NaN in d reaches C (the max keeps it), every value and every gradient element.
+ *   TULIP_LOSS_L1     tulip_l1_loss_fwd / _bwd's arithmetic (the training step keeps calling those)
+ * Flat kernels: tulip_loss_blocks(n) = min(1024, ceil(ceil(n / 4) / 256)) workgroups of 256 threads, float4 loads where pred,
+ * target (and dpred) are 16-byte aligned and a scalar tail, every reduction in a fixed order (deterministic), plain stores, no
+ * atomics, graph-capturable.  losses[1] stays the L1 metric of tulip_l1_loss_fwd for every kind.
+ *   tulip_loss_stats  one pass: stats[4 wg + {0, 1, 2, 3}] = {sum |d|, sum |expm1(pred) - expm1(target)| (log_transform, else 0),
+ *                     sum d^2, max |d| (NaN-keeping)} per workgroup; stats: 4 * TULIP_LOSS_BLOCKS_MAX floats, 16-byte aligned
+ *   tulip_loss_bwd    dpred[i] = g * grad_kind(d_i; C), g = fl32((gscale_dev ? gscale_dev[0] : gscale) / n).  BERHU: every workgroup
+ *                     folds the maxima of `stats` itself (max is exact: the same C everywhere) and loss_c[0] = C is written;
+ *                     other kinds read neither stats nor loss_c (both may be NULL)
+ *   tulip_loss_value  BERHU's second pass (the sum needs C): value_partials[wg] = the workgroup's sum of the elementwise values;
+ *                     value_partials: TULIP_LOSS_BLOCKS_MAX floats
+ *   tulip_loss_final  one workgroup, the partials folded in double: losses[0] = the loss of `kind`, losses[1] = the mean of
+ *                     stats' second sums (log_transform) or of the first.  value_partials is read for BERHU only
+ * TULIP_ERR_ARG before any launch: an unknown kind, n <= 0, a NULL required pointer, a misaligned stats. */
+#define TULIP_LOSS_L1 0
+#define TULIP_LOSS_L2 1
+#define TULIP_LOSS_BERHU 2
+#define TULIP_LOSS_BLOCKS_MAX 1024
+int tulip_loss_blocks(int64_t n);
+int tulip_loss_stats(const float* pred, const float* target, float* stats, int64_t n, int log_transform, hipStream_t stream);
+int tulip_loss_bwd(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev, float gscale,
+                   float* dpred, float* loss_c, int64_t n, hipStream_t stream);
+int tulip_loss_value(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n,
+                     hipStream_t stream);
+int tulip_loss_final(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, int log_transform,
+                     hipStream_t stream);
+
 /* Fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, main_lidar_upsampling.py:283):
  * hyper (device, 8 floats) = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}.
  * decay_mask64[i/64] bit 0 selects weight decay for elements of 64-float block i/64 (timm's grouping,

@@ -1,0 +1,74 @@
+"""Step time of the captured training step per training loss (profiles/README.md, "Training loss"): bench.py's model, batch and
+timing loop -- tulip_base KITTI 16x1024 -> 64x1024, batch 8, 10 warm-up steps, then 50 timed steps between two synchronisations,
+wall clock -- on three Trainers, interleaved, each run in a process of its own (bench.py has no switch for the loss;
+tools/bench_guard.py is the model):
+
+    l1       TULIP(...)                  the default: the head kernels form sign(pred - target) / n themselves
+    l2       TULIP(..., loss="l2")       + tulip_loss_bwd on the chain in front of the head's backward (the statistics pass beside it)
+    berhu    TULIP(..., loss="berhu")    + tulip_loss_stats behind the head's forward and tulip_loss_bwd in front of its backward
+
+    python tools/bench_loss.py [--rounds 3]          one JSON line per run, then a summary line (per arm: the runs, min, max)
+    python tools/bench_loss.py --one l1|l2|berhu     a single run in this process (what the driver starts)
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+VARIANTS = ("l1", "l2", "berhu")
+
+
+def one(variant: str, steps: int, warmup: int) -> dict:
+    import torch
+    from tulip_amd.model import tulip as T
+    import bench
+    from tulip_amd.trainer import Trainer
+    args = argparse.Namespace(model="tulip_base", img=[16, 1024], target=[64, 1024], batch=8)
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)                     # bench.make_model's model, with the loss keyword
+    model = T.tulip_base(img_size=tuple(args.img), target_img_size=tuple(args.target), patch_size=(1, 4), in_chans=1,
+                         window_size=[2, 8], swin_v2=False, pixel_shuffle=True, circular_padding=True, log_transform=True,
+                         patch_unmerging=True, loss=variant).to(dev).train()
+    tr = Trainer(model, 8, lr=5e-4, betas=(0.9, 0.95), weight_decay=0.01, device=dev)
+    tr.load_batch(*bench.synthetic(args, 0, dev))
+    for _ in range(warmup):
+        tr.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        tr.step()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return {"variant": variant, "ms_per_step": round(dt / steps * 1e3, 4), "loss": float(tr.P.losses[0]),
+            "pixel_loss": float(tr.P.losses[1]), "loss_c": float(tr.loss_c) if variant == "berhu" else None}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--one", choices=list(VARIANTS))
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    a = ap.parse_args()
+    if a.one is not None:
+        print(json.dumps(one(a.one, a.steps, a.warmup)), flush=True)
+        return
+    res = {v: [] for v in VARIANTS}
+    for _ in range(a.rounds):
+        for v in VARIANTS:
+            r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--one", v, "--steps", str(a.steps),
+                                "--warmup", str(a.warmup)], capture_output=True, text=True)
+            if r.returncode != 0:
+                sys.exit(f"run failed ({r.returncode}):\n{r.stdout[-1000:]}{r.stderr[-3000:]}")
+            line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+            print(line, flush=True)
+            res[v].append(json.loads(line)["ms_per_step"])
+    print(json.dumps({"ms_per_step": res, "spread": {v: [min(x), max(x)] for v, x in res.items()}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

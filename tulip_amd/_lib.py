@@ -88,6 +88,7 @@ GEMM_B_PACKED = 0x1000
 # tulip_gemm_route's bit field (TULIP_ROUTE_* of tulip_hip.h)
 ROUTE_TILE, ROUTE_FULL, ROUTE_MID, ROUTE_STREAM = range(4)
 ROUTE_DEEP, ROUTE_A_TRANS, ROUTE_B_TRANS, ROUTE_FOLD, ROUTE_SPLITS_SHIFT = 0x10, 0x20, 0x40, 0x80, 8
+LOSS_L1, LOSS_L2, LOSS_BERHU, LOSS_BLOCKS_MAX = 0, 1, 2, 1024      # TULIP_LOSS_* of tulip_hip.h
 ABI_VERSION = 6      # TULIP_ABI_VERSION of include/tulip_hip.h: the ctypes structs above mirror that layout
 
 # name -> argtypes (must mirror include/tulip_hip.h; tests/test_cabi.py cross-checks against the header)
@@ -174,6 +175,12 @@ SIGNATURES = {
     "tulip_expand_norm_bwd_c": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I],
     "tulip_l1_loss_fwd": [P, P, P, P, L, I, P],
     "tulip_l1_loss_bwd": [P, P, P, F, P, L, P],
+    # the selectable training loss (csrc/loss.hip; kinds LOSS_L1 / LOSS_L2 / LOSS_BERHU below)
+    "tulip_loss_blocks": [L],
+    "tulip_loss_stats": [P, P, P, L, I, P],
+    "tulip_loss_bwd": [I, P, P, P, P, F, P, P, L, P],
+    "tulip_loss_value": [P, P, P, P, L, P],
+    "tulip_loss_final": [I, P, P, P, L, I, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
     # ... and with a trailing-but-one lr_scale64 table: per-group learning-rate scales (group = mask byte >> 2)

@@ -24,7 +24,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import knobs, ops
+from . import _lib, knobs, ops
+from .loss import check_loss
 from ._lib import (EPI_BF16, EPI_F32, EPI_GELU_BWD, EPI_GELU_DUAL, EPI_PIXSHUF2_F32, EPI_RESID_F32,
                    EPI_UNSHUF2_BF16,
                    EPI_SPLIT_F32)
@@ -289,6 +290,12 @@ class Plan:
         self.partials = self.f32("partials", max(2048, 2 * ((B * H0 * W0 + 31) // 32)))   # loss partial sums (2 per block)
         self.gscale = self.f32("gscale", 1)
         self.gscale.fill_(1.0)
+        if eng.loss_kind != "l1":
+            # TULIP(loss="l2" | "berhu") (tulip_amd/loss.py): the per-workgroup partials of tulip_loss_stats / tulip_loss_value and
+            # berHu's threshold C = 0.2 max|pred - target| as the backward formed it (a device float, never read back by the step)
+            self.loss_stats = self.f32("loss_stats", 4 * _lib.LOSS_BLOCKS_MAX).zero_()
+            self.loss_vpart = self.f32("loss_vpart", _lib.LOSS_BLOCKS_MAX).zero_()
+            self.loss_c = self.f32("loss_c", 1).zero_()
         nslots = max(1, eng.n_drop_slots)
         self.drop_scale = self.f32("drop_scale", nslots, B)
         self.drop_scale.fill_(1.0)
@@ -1049,6 +1056,31 @@ class TulipEngine:
     fuse_tail_fwd = True      # norm_up + head + loss partials in one launch
     _loss_final = None
 
+    @property
+    def loss_kind(self) -> str:
+        """The model's training loss (TULIP(loss=...), tulip_amd/loss.py); "l1" for a model object without the attribute."""
+        return check_loss(getattr(self.model, "loss", "l1"))
+
+    def _loss_fwd(self, P: Plan, kind: str, defer: bool):
+        """The loss read-out of a loss other than L1 behind the head's forward: tulip_loss_stats (berHu: at once -- its maxima are
+        what the backward forms C from, on the device; L2: with the rest), then -- beside the chain when `defer` (run_backward
+        issues it; nothing on the GPU reads `losses`) -- berHu's value pass and the final fold."""
+        n, lt = P.pred.numel(), self.model.log_transform
+        stats = lambda: ops.loss_stats(P.pred, P.target, P.loss_stats, n, lt)
+        if kind == "berhu":
+            stats()
+
+        def fin():
+            if kind == "berhu":
+                ops.loss_value(P.pred, P.target, P.loss_stats, P.loss_vpart, n)
+            else:
+                stats()
+            ops.loss_final(kind, P.loss_stats, P.loss_vpart, P.losses, n, lt)
+        if defer:
+            self._loss_final = fin
+        else:
+            fin()
+
     def run_forward(self, P: Plan, with_loss: bool = True, pack_on_side: bool = False, defer_loss_final: bool = False):
         """TULIP.forward (tulip.py:702-737) on P.x_in / P.target -> P.pred, P.losses.
         pack_on_side (Trainer): the fragment-major weight copies of the fused wide blocks are rewritten from the bf16
@@ -1156,14 +1188,18 @@ class TulipEngine:
                                 out_bf16=P[f"lvl{s}.xb"] if i < nl - 2 else None)
         M0 = B * H0 * W0
         loss_done = False
+        kind = self.loss_kind
+        l1 = with_loss and kind == "l1"            # the L1 partial sums ride in the head's forward; another loss reads pred behind it
         if m.pixel_shuffle and self.fuse_tail_fwd:
             # norm_up -> expand conv -> LeakyReLU -> PixelShuffle(4) -> decoder_pred (-> L1 partial sums) in ONE launch
             ops.tail_fwd_ln(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), self.eps, P["tail.xn"], P["tail.mean"],
                             P["tail.rstd"], W_.p16("ps_head.conv_expand.0.weight"), W_.p32("ps_head.conv_expand.0.bias"),
-                            W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, target=P.target if with_loss else None,
-                            loss_partials=P.partials if with_loss else None, log_transform=m.log_transform,
+                            W_.p32("decoder_pred.weight"), P.pred, B, H0, W0, E, target=P.target if l1 else None,
+                            loss_partials=P.partials if l1 else None, log_transform=m.log_transform,
                             in_chans=m.in_chans, r=m.upscale_factor)
-            if with_loss:
+            if with_loss and not l1:
+                self._loss_fwd(P, kind, defer_loss_final)
+            elif with_loss:
                 fin = lambda: ops.l1_loss_final(P.partials, P.losses, (M0 + 31) // 32, P.pred.numel(), m.log_transform)
                 if defer_loss_final:
                     self._loss_final = fin            # run_backward issues it beside the chain (nothing on the GPU reads it)
@@ -1188,7 +1224,9 @@ class TulipEngine:
                                 P["tail.erstd"], B, H0, W0, r, E, self.eps, dotw=W_.p32("decoder_pred.weight"),
                                 pred=P.pred, in_chans=m.in_chans)
         self._join_pack()                          # (a model without fused wide blocks never asked for the copies)
-        if with_loss and not loss_done:
+        if with_loss and not loss_done and not l1:
+            self._loss_fwd(P, kind, False)
+        elif with_loss and not loss_done:
             ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform)
         P.generation += 1
         P.last_x = x
@@ -1887,14 +1925,21 @@ class TulipEngine:
 
         M0 = B * H0 * W0
         gdw = G("decoder_pred.weight")
+        kind = self.loss_kind
+        if kind != "l1":
+            # d(loss)/d(pred) of the chosen loss in front of the head (csrc/loss.hip; berHu forms C from the forward's maxima in this
+            # launch): the head kernels then take their `target == NULL` route -- dpred is the upstream gradient, gscale inside it
+            ops.loss_bwd(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel())
         if m.pixel_shuffle:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
-            targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred)
+            targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred if kind == "l1" else P.dpred)
             r = m.upscale_factor
             NE = r * r * E                              # output channels of the expand conv
             tkw = dict(target=P.target, gscale_dev=gscale_dev, gscale=gscale,   # L1 backward (tulip.py:692-693) formed in-kernel
                        in_chans=m.in_chans, r=r)
+            if kind != "l1":
+                tkw.update(target=None, gscale_dev=None, gscale=1.0)
             self._tail_fused = self.fuse_tail_bwd and ops.tail_fused_bwd_supported(E, r)
             if self._tail_fused:
                 # d(expand pre-activation) -- 100 MB at batch 8 -- is never written: the chain's kernel goes straight to dxn,
@@ -1935,7 +1980,8 @@ class TulipEngine:
             r = m.upscale_factor
             NE = r * r * E
             pre = "final_patch_expanding"
-            ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
+            if kind == "l1":
+                ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
             R = ops.expand_norm_bwd_partial_rows(B, H0, W0, r)
             nrow = (2 + m.in_chans) * E                 # [dgamma | dbeta | d(decoder_pred.weight) (in_chans, E)]
             part = P.scratch("exp.final", R * nrow)
@@ -2114,7 +2160,7 @@ class TulipEngine:
         # argument) and the number of draw slots
         key = key + (self.fuse_wide, self.fuse_wide_bwd, self.fuse_block96, self.fuse_block96_bwd, self.split_wide, self.split_wide_bwd,
                      self.fc1_grad_wide, self.fc1_grad96, self.recompute96, self.fuse_deep, self.fuse_tail_fwd, self.fuse_tail_bwd, self.fuse_glue, self.pair96, self.packed_gemm,
-                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state())
+                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind)
         ent = graphs.get(key)
         if not self.graph_module or ent is None:
             fn()

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..loss import check_loss
+
 __all__ = ["TULIP", "tulip_base", "tulip_large"]
 
 
@@ -171,15 +173,22 @@ class BasicBlockUp(_ParamHolder):  # tulip.py:441-475
 
 
 class TULIP(nn.Module):
-    """tulip.py:530-737.  Constructor signature and defaults are the reference's."""
+    """tulip.py:530-737.  Constructor signature and defaults are the reference's, followed by one keyword of this project's:
+
+    loss: "l1" (default: the reference's forward_loss, tulip.py:690-700), "l2" or "berhu" -- the training loss `forward` returns
+    as total_loss and `loss.backward()` / Trainer differentiate (tulip_amd/loss.py is the definition; ValueError for another
+    name).  berHu's threshold C = 0.2 max|pred - target| is formed on the device per call: per micro-batch under gradient
+    accumulation and per rank with world > 1, as in the reference, where every rank computes its own loss.  pixel_loss, the third
+    value, stays the L1 metric for every kind.  Fixed at construction; state_dict() does not carry it."""
 
     def __init__(self, img_size=(32, 2048), target_img_size=(128, 2048), patch_size=(4, 4), in_chans: int = 1,
                  embed_dim: int = 96, window_size=4, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
                  mlp_ratio: float = 4.0, qkv_bias: bool = True, drop_rate: float = 0.0, attn_drop_rate: float = 0.0,
                  drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True,
                  pixel_shuffle: bool = False, circular_padding: bool = False, swin_v2: bool = False,
-                 log_transform: bool = False, patch_unmerging: bool = False):
+                 log_transform: bool = False, patch_unmerging: bool = False, loss: str = "l1"):
         super().__init__()
+        self._loss = check_loss(loss)
         self.window_size = window_size
         self.depths, self.num_heads = tuple(depths), tuple(num_heads)
         self.num_layers = len(depths)
@@ -241,6 +250,11 @@ class TULIP(nn.Module):
         elif isinstance(m, nn.LayerNorm):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
+
+    @property
+    def loss(self) -> str:
+        """the training loss chosen at construction (the engine's plans and captured graphs are built for it)"""
+        return self._loss
 
     # ------------------------------------------------------------------ engine plumbing
     def engine(self):

@@ -370,6 +370,40 @@ def l1_loss_bwd(pred, target, gscale_dev, gscale, dpred, n):
                                         _stream()), "tulip_l1_loss_bwd")
 
 
+LOSS_KINDS = {"l1": _lib.LOSS_L1, "l2": _lib.LOSS_L2, "berhu": _lib.LOSS_BERHU}      # tulip_amd/loss.py names -> TULIP_LOSS_*
+
+
+def _loss_kind(kind) -> int:
+    return LOSS_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def loss_blocks(n):
+    """workgroups of the tulip_loss_* launches over n elements: the rows of `stats` (4 floats each) and of `value_partials`"""
+    return _lib.load().tulip_loss_blocks(n)
+
+
+def loss_stats(pred, target, stats, n, log_transform):
+    """stats (4 * LOSS_BLOCKS_MAX floats): per workgroup [sum |d|, sum |expm1 p - expm1 t|, sum d^2, max |d|]."""
+    check(_lib.load().tulip_loss_stats(_p(pred), _p(target), _p(stats), n, int(log_transform), _stream()), "tulip_loss_stats")
+
+
+def loss_bwd(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n):
+    """dpred = gscale * d(loss of `kind`) / d(pred) (tulip_amd/loss.py); berhu reads stats' maxima and writes loss_c[0] = C."""
+    check(_lib.load().tulip_loss_bwd(_loss_kind(kind), _p(pred), _p(target), _p(stats), _p(gscale_dev), float(gscale), _p(dpred),
+                                     _p(loss_c), n, _stream()), "tulip_loss_bwd")
+
+
+def loss_value(pred, target, stats, value_partials, n):
+    """berhu's second pass: value_partials (LOSS_BLOCKS_MAX floats) = per-workgroup sums of the elementwise values."""
+    check(_lib.load().tulip_loss_value(_p(pred), _p(target), _p(stats), _p(value_partials), n, _stream()), "tulip_loss_value")
+
+
+def loss_final(kind, stats, value_partials, losses, n, log_transform):
+    """losses[0] = the loss of `kind`, losses[1] = pixel_loss (the L1 metric), from the partials of loss_stats / loss_value."""
+    check(_lib.load().tulip_loss_final(_loss_kind(kind), _p(stats), _p(value_partials), _p(losses), n, int(log_transform),
+                                       _stream()), "tulip_loss_final")
+
+
 def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None, skip=None):
     """lr_scale64: per-group learning-rate scales (pack_lr_groups; tulip_adamw_s) -- None: tulip_adamw.
     skip: the non-finite guard's device flag (step_guard; tulip_adamw_g) -- None: the entry points without it."""

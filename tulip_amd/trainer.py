@@ -36,6 +36,7 @@ from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
 from .guard import check_skip_nonfinite
+from .loss import check_loss
 from .engine import ALIGN
 
 
@@ -112,8 +113,16 @@ class Trainer:
         are (the gradients are still cleared where a taken step clears them) and counts the step as skipped; the optimizer's step
         count and the bias corrections follow the APPLIED steps, on the device.  With world > 1 the norm is that of the all-reduced
         gradient: every rank decides alike.  Read-outs: last_step_skipped (device uint32, no sync), skipped_steps, applied_steps,
-        consecutive_skips (ints, one host sync each).  exchange="sharded" with skip_nonfinite raises ValueError."""
+        consecutive_skips (ints, one host sync each).  exchange="sharded" with skip_nonfinite raises ValueError.
+        The training loss is the model's (TULIP(loss="l1" | "l2" | "berhu"), tulip_amd/loss.py): no argument here.  `losses[0]` is
+        that loss, `losses[1]` stays the L1 metric.  berHu's threshold C is formed on the device inside the captured graphs, per
+        micro-batch under accum_iter > 1 and per rank with world > 1 (as in the reference, where every rank computes its own
+        loss); `loss_c` is the device float of the last backward.  exchange="sharded" with a loss other than "l1" raises
+        ValueError (that plan is optional and unmeasured)."""
         skip_nonfinite = check_skip_nonfinite(skip_nonfinite)
+        self.loss = check_loss(getattr(model, "loss", "l1"))
+        if self.loss != "l1" and exchange == "sharded":
+            raise ValueError("exchange='sharded' with a loss other than 'l1' is not supported: use exchange='allreduce'")
         if skip_nonfinite and exchange == "sharded":
             raise ValueError("exchange='sharded' with skip_nonfinite is not supported (the per-bucket optimizer steps before the "
                              "global norm exists): use exchange='allreduce'")
@@ -333,6 +342,13 @@ class Trainer:
             self._clip_max.copy_(torch.full((1,), self._clip_grad, dtype=torch.float32))
 
     # ------------------------------------------------------------------ non-finite guard
+    @property
+    def loss_c(self) -> torch.Tensor:
+        """berHu's threshold C = 0.2 max|pred - target| of the last backward: a device float (no sync); loss="berhu" only."""
+        if self.loss != "berhu":
+            raise AttributeError("this Trainer's model has no berHu threshold: build the model with loss='berhu'")
+        return self.P.loss_c
+
     def _guard_word(self, k: int) -> int:
         if self._guard_state is None:
             raise AttributeError("this Trainer has no non-finite guard: build it with skip_nonfinite=True")

@@ -498,6 +498,36 @@ int tulip_loss_value(const float* pred, const float* target, const float* stats,
 int tulip_loss_final(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, int log_transform,
                      hipStream_t stream);
 
+/* The masked forms, TULIP(loss_valid_min=v) (host definition: tulip_amd/loss.py): the same four launches over the VALID elements.
+ * pred / target are (B, chans, chan_stride) with n = B * chans * chan_stride; pixel (b, pix) is valid iff
+ * target[b, 0, pix] > valid_min -- channel 0, the range; false for a NaN -- and all `chans` elements of a valid pixel count:
+ * n_v = chans * (valid pixels) stands where n stands above (L1: sum|d| / n_v, gradient sign(d) / n_v; L2: sum d^2 / n_v, 2 d / n_v;
+ * BERHU: C = 0.2f * max over the valid |d|, values and gradient as above with n_v; losses[1]: the L1 metric over the valid
+ * elements).  The gradient at an invalid element is +0.0f.  n_v == 0: losses, C and every gradient are 0.  Whatever pred or any
+ * channel of target holds at an invalid pixel (a NaN, an infinity; a NaN in target[b, 0, pix] makes the pixel invalid) changes
+ * nothing; a non-finite value at a valid element propagates as above.  For chans == 1 the mask is the element's own target value
+ * (no second load); for chans > 1 the kernels read target[b, 0, pix].  Same grid, same fixed reduction orders, plain stores, no
+ * atomics; float4 loads only where pred, target (and dpred) are 16-byte aligned AND chan_stride % 4 == 0 (a group then never
+ * straddles a channel, and target's channel-0 rows are aligned too), the scalar route otherwise.
+ *   tulip_loss_stats_m  stats as above over the valid elements (the NaN-keeping max too), and counts[wg] = the workgroup's number
+ *                       of valid elements (integers: per thread, the wave tree, four wave results); counts:
+ *                       TULIP_LOSS_BLOCKS_MAX uint32
+ *   tulip_loss_bwd_m    every workgroup folds `counts` itself (integer addition is exact in any order: the same n_v everywhere);
+ *                       g = fl32(gscale / (float)n_v), one rounding; n_valid[0] = n_v.  stats / loss_c as in tulip_loss_bwd
+ *   tulip_loss_value_m  BERHU's second pass over the valid elements (n_v == 0: zeros, nothing read)
+ *   tulip_loss_final_m  1 / (double)n_v formed on the device (0 when n_v == 0); n_valid[0] = n_v
+ * TULIP_ERR_ARG before any launch, besides the cases above: chans < 1, chan_stride < 1, n no multiple of chans * chan_stride,
+ * n >= 2^41, a NaN or infinite valid_min, a NULL or misaligned counts / n_valid. */
+int tulip_loss_stats_m(const float* pred, const float* target, float* stats, int64_t n, int log_transform, int chans,
+                       int64_t chan_stride, float valid_min, uint32_t* counts, hipStream_t stream);
+int tulip_loss_bwd_m(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev, float gscale,
+                     float* dpred, float* loss_c, int64_t n, int chans, int64_t chan_stride, float valid_min,
+                     const uint32_t* counts, int64_t* n_valid, hipStream_t stream);
+int tulip_loss_value_m(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n, int chans,
+                       int64_t chan_stride, float valid_min, const uint32_t* counts, hipStream_t stream);
+int tulip_loss_final_m(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, int log_transform,
+                       const uint32_t* counts, int64_t* n_valid, hipStream_t stream);
+
 /* Fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, main_lidar_upsampling.py:283):
  * hyper (device, 8 floats) = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}.
  * decay_mask64[i/64] bit 0 selects weight decay for elements of 64-float block i/64 (timm's grouping,

@@ -1,14 +1,19 @@
 """Step time of the captured training step per training loss (profiles/README.md, "Training loss"): bench.py's model, batch and
 timing loop -- tulip_base KITTI 16x1024 -> 64x1024, batch 8, 10 warm-up steps, then 50 timed steps between two synchronisations,
-wall clock -- on three Trainers, interleaved, each run in a process of its own (bench.py has no switch for the loss;
+wall clock -- on six Trainers, interleaved, each run in a process of its own (bench.py has no switch for the loss;
 tools/bench_guard.py is the model):
 
     l1       TULIP(...)                  the default: the head kernels form sign(pred - target) / n themselves
     l2       TULIP(..., loss="l2")       + tulip_loss_bwd on the chain in front of the head's backward (the statistics pass beside it)
     berhu    TULIP(..., loss="berhu")    + tulip_loss_stats behind the head's forward and tulip_loss_bwd in front of its backward
+    l1_m, l2_m, berhu_m                  the same losses over the valid pixels only, TULIP(..., loss_valid_min=0.0), on the seeded batch
+                                         (10 % of its target pixels are 0): tulip_loss_stats_m behind the head's forward and
+                                         tulip_loss_bwd_m in front of its backward, for every kind
 
     python tools/bench_loss.py [--rounds 3]          one JSON line per run, then a summary line (per arm: the runs, min, max)
-    python tools/bench_loss.py --one l1|l2|berhu     a single run in this process (what the driver starts)
+    python tools/bench_loss.py --parent DIR          ... with one more arm, "parent_l1": the `l1` run of the built checkout of another
+                                                     commit at DIR (its own tools/bench_loss.py --one l1), in every round
+    python tools/bench_loss.py --one l1|l2|berhu|l1_m|l2_m|berhu_m     a single run in this process (what the driver starts)
 """
 import argparse
 import json
@@ -19,7 +24,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-VARIANTS = ("l1", "l2", "berhu")
+KINDS = ("l1", "l2", "berhu")
+VARIANTS = KINDS + tuple(k + "_m" for k in KINDS)
 
 
 def one(variant: str, steps: int, warmup: int) -> dict:
@@ -29,10 +35,11 @@ def one(variant: str, steps: int, warmup: int) -> dict:
     from tulip_amd.trainer import Trainer
     args = argparse.Namespace(model="tulip_base", img=[16, 1024], target=[64, 1024], batch=8)
     dev = torch.device("cuda", 0)
-    torch.manual_seed(0)                     # bench.make_model's model, with the loss keyword
+    kind, masked = variant.replace("_m", ""), variant.endswith("_m")
+    torch.manual_seed(0)                     # bench.make_model's model, with the loss keywords
     model = T.tulip_base(img_size=tuple(args.img), target_img_size=tuple(args.target), patch_size=(1, 4), in_chans=1,
                          window_size=[2, 8], swin_v2=False, pixel_shuffle=True, circular_padding=True, log_transform=True,
-                         patch_unmerging=True, loss=variant).to(dev).train()
+                         patch_unmerging=True, loss=kind, **(dict(loss_valid_min=0.0) if masked else {})).to(dev).train()
     tr = Trainer(model, 8, lr=5e-4, betas=(0.9, 0.95), weight_decay=0.01, device=dev)
     tr.load_batch(*bench.synthetic(args, 0, dev))
     for _ in range(warmup):
@@ -44,7 +51,8 @@ def one(variant: str, steps: int, warmup: int) -> dict:
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return {"variant": variant, "ms_per_step": round(dt / steps * 1e3, 4), "loss": float(tr.P.losses[0]),
-            "pixel_loss": float(tr.P.losses[1]), "loss_c": float(tr.loss_c) if variant == "berhu" else None}
+            "pixel_loss": float(tr.P.losses[1]), "loss_c": float(tr.loss_c) if kind == "berhu" else None,
+            "loss_valid": int(tr.loss_valid) if masked else None}
 
 
 def main():
@@ -53,20 +61,24 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--parent", help="a built checkout of another commit: its l1 arm runs beside these")
     a = ap.parse_args()
     if a.one is not None:
         print(json.dumps(one(a.one, a.steps, a.warmup)), flush=True)
         return
-    res = {v: [] for v in VARIANTS}
+    arms = (("parent_l1",) if a.parent else ()) + VARIANTS
+    res = {v: [] for v in arms}
     for _ in range(a.rounds):
-        for v in VARIANTS:
-            r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--one", v, "--steps", str(a.steps),
-                                "--warmup", str(a.warmup)], capture_output=True, text=True)
+        for v in arms:
+            script = os.path.join(os.path.abspath(a.parent), "tools", "bench_loss.py") if v == "parent_l1" else os.path.abspath(__file__)
+            r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, script, "--one", "l1" if v == "parent_l1" else v,
+                                "--steps", str(a.steps), "--warmup", str(a.warmup)], capture_output=True, text=True)
             if r.returncode != 0:
                 sys.exit(f"run failed ({r.returncode}):\n{r.stdout[-1000:]}{r.stderr[-3000:]}")
-            line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-            print(line, flush=True)
-            res[v].append(json.loads(line)["ms_per_step"])
+            line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+            line["variant"] = v
+            print(json.dumps(line), flush=True)
+            res[v].append(line["ms_per_step"])
     print(json.dumps({"ms_per_step": res, "spread": {v: [min(x), max(x)] for v, x in res.items()}}), flush=True)
 
 

@@ -181,6 +181,11 @@ SIGNATURES = {
     "tulip_loss_bwd": [I, P, P, P, P, F, P, P, L, P],
     "tulip_loss_value": [P, P, P, P, L, P],
     "tulip_loss_final": [I, P, P, P, L, I, P],
+    # ... over the valid pixels only (TULIP(loss_valid_min=...)): + chans, chan_stride, valid_min, counts (, n_valid)
+    "tulip_loss_stats_m": [P, P, P, L, I, I, L, F, P, P],
+    "tulip_loss_bwd_m": [I, P, P, P, P, F, P, P, L, I, L, F, P, P, P],
+    "tulip_loss_value_m": [P, P, P, P, L, I, L, F, P, P],
+    "tulip_loss_final_m": [I, P, P, P, L, I, P, P, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
     # ... and with a trailing-but-one lr_scale64 table: per-group learning-rate scales (group = mask byte >> 2)

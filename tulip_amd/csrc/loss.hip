@@ -1,6 +1,6 @@
 // The selectable training loss, TULIP(loss="l2" | "berhu") (tulip_amd/loss.py is the host definition): four flat, HBM-bound
-// kernels over n = pred.numel() elements.  float4 loads where pred / target (/ dpred) are 16-byte aligned, a scalar tail behind
-// them; at most 1024 workgroups of 256 threads; every reduction in a fixed order (per-thread grid-stride sums, the wave tree,
+// kernels over n = pred.numel() elements, and their masked forms (TULIP(loss_valid_min=...), the _m entry points: LossMask
+// below).  float4 loads where pred / target (/ dpred) are 16-byte aligned, a scalar tail behind them; at most 1024 workgroups of 256 threads; every reduction in a fixed order (per-thread grid-stride sums, the wave tree,
 // four wave results in a fixed bracket, the final fold in double by one workgroup): the same bits run to run.  Plain vector
 // stores only, no atomics.   gfx950 only.
 #include "common.h"
@@ -47,8 +47,56 @@ __device__ __forceinline__ float berhu_threshold(const float* __restrict__ stats
     return 0.2f * m;
 }
 
+// The valid-pixel mask of the _m entry points (TULIP(loss_valid_min=...)): element e = (b * chans + c) * chan_stride + pix of
+// (pred, target) counts iff target[b, 0, pix] > valid_min (false for a NaN) -- channel 0, the range.  chans == 1: that is the
+// element's own target value, no second load.  The kernels take this struct as a trailing parameter pack K..., LossMask for the
+// masked instantiations and empty for the unmasked ones, whose arguments and code are thereby what they were without it.
+struct LossMask {
+    int64_t chan_stride;       // H * W
+    int chans;
+    int narrow;                // n < 2^32: the index arithmetic in 32 bits
+    float valid_min;
+    uint32_t* counts;          // [TULIP_LOSS_BLOCKS_MAX]: the valid elements each workgroup of loss_stats_kernel saw
+    int64_t* n_valid;          // n_v = their sum, as the bwd / final kernel formed it
+};
+
+__device__ __forceinline__ LossMask mask_arg() { return LossMask{}; }
+__device__ __forceinline__ LossMask mask_arg(const LossMask& k) { return k; }
+
+// the index of target[b, 0, pix] for element e.  On the float4 route (chan_stride % 4 == 0) e is a multiple of 4 and so is the
+// result: a group never straddles a channel
+__device__ __forceinline__ int64_t chan0_index(int64_t e, const LossMask& k) {
+    if (k.narrow) {
+        const uint32_t hw = (uint32_t)k.chan_stride, cs = hw * (uint32_t)k.chans, u = (uint32_t)e, base = u - u % cs;
+        return base + (u - base) % hw;
+    }
+    const int64_t cs = k.chan_stride * k.chans, base = e - e % cs;
+    return base + (e - base) % k.chan_stride;
+}
+// the mask values of the float4 group at element e, whose own target values are t / of the single element e
+__device__ __forceinline__ float4 mask_src4(const float* __restrict__ tgt, int64_t e, float4 t, const LossMask& k) {
+    if (k.chans != 1) t = *(const float4*)(tgt + chan0_index(e, k));
+    return t;
+}
+__device__ __forceinline__ float mask_src(const float* __restrict__ tgt, int64_t e, float t, const LossMask& k) {
+    if (k.chans != 1) t = tgt[chan0_index(e, k)];
+    return t;
+}
+
+// n_v = the sum of the per-workgroup counts (counts[wg], wg < nb <= 1024), folded by every workgroup itself: integer addition is
+// exact in any order, so every workgroup holds the same n_v
+__device__ __forceinline__ int64_t valid_count(const uint32_t* __restrict__ counts, int nb, long long* red) {
+    long long c = 0;
+    for (int i = threadIdx.x; i < nb; i += 256) c += counts[i];
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 struct LossAcc {
     float abs = 0.f, pix = 0.f, sq = 0.f, mx = 0.f;
+    uint32_t cnt = 0;          // the valid elements (masked kernels only)
     __device__ __forceinline__ void add(float p, float t, int log_transform) {
         const float d = p - t, a = fabsf(d);
         abs += a;
@@ -56,20 +104,50 @@ struct LossAcc {
         sq += d * d;
         mx = nan_max(mx, a);
     }
+    // an invalid element enters nothing: whatever p and t hold there (a NaN, an infinity) stays out of the sums and the max
+    __device__ __forceinline__ void add_if(bool valid, float p, float t, int log_transform) {
+        if (valid) {
+            add(p, t, log_transform);
+            ++cnt;
+        }
+    }
 };
 
-// stats[4 wg + {0, 1, 2, 3}] = {sum |d|, sum |expm1 p - expm1 t| (log_transform, else 0), sum d^2, max |d|} of the workgroup
+// stats[4 wg + {0, 1, 2, 3}] = {sum |d|, sum |expm1 p - expm1 t| (log_transform, else 0), sum d^2, max |d|} of the workgroup;
+// MASK: over the valid elements, and k.counts[wg] = how many there were
+template <class... K>
 __global__ __launch_bounds__(256) void loss_stats_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                         float* __restrict__ stats, int64_t n, int64_t n4, int log_transform) {
+                                                         float* __restrict__ stats, int64_t n, int64_t n4, int log_transform,
+                                                         K... kk) {
+    constexpr bool MASK = sizeof...(K) != 0;
+    const LossMask k = mask_arg(kk...);
     __shared__ float red[4][4];
     LossAcc s;
     const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
     for (int64_t i = first; i < n4; i += stride) {
         const float4 p = *(const float4*)(pred + i * 4), t = *(const float4*)(tgt + i * 4);
-        s.add(p.x, t.x, log_transform); s.add(p.y, t.y, log_transform);
-        s.add(p.z, t.z, log_transform); s.add(p.w, t.w, log_transform);
+        if constexpr (MASK) {
+            const float4 z = mask_src4(tgt, i * 4, t, k);
+            s.add_if(z.x > k.valid_min, p.x, t.x, log_transform); s.add_if(z.y > k.valid_min, p.y, t.y, log_transform);
+            s.add_if(z.z > k.valid_min, p.z, t.z, log_transform); s.add_if(z.w > k.valid_min, p.w, t.w, log_transform);
+        } else {
+            s.add(p.x, t.x, log_transform); s.add(p.y, t.y, log_transform);
+            s.add(p.z, t.z, log_transform); s.add(p.w, t.w, log_transform);
+        }
     }
-    for (int64_t i = n4 * 4 + first; i < n; i += stride) s.add(pred[i], tgt[i], log_transform);
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        if constexpr (MASK) s.add_if(mask_src(tgt, i, tgt[i], k) > k.valid_min, pred[i], tgt[i], log_transform);
+        else s.add(pred[i], tgt[i], log_transform);
+    }
+    if constexpr (MASK) {
+        // integers: per thread, the wave tree, four wave results
+        __shared__ uint32_t cred[4];
+        uint32_t c = s.cnt;
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) k.counts[blockIdx.x] = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+    }
     block_sum(s.abs, red, 0);
     block_sum(s.pix, red, 1);
     block_sum(s.sq, red, 2);
@@ -92,54 +170,110 @@ __device__ __forceinline__ float loss_grad(float p, float t, float C, float g) {
     else return berhu_grad(d, C, g);
 }
 
-// dpred[i] = g * grad_kind(d_i; C), g = gscale / n (one rounding, as in tulip_l1_loss_bwd)
-template <int KIND>
+// dpred[i] = g * grad_kind(d_i; C), g = gscale / n (one rounding, as in tulip_l1_loss_bwd).  MASK: n_v (folded here, written to
+// k.n_valid) in place of n, C from the valid maxima, +0 at the invalid elements -- and everywhere when n_v == 0
+template <int KIND, class... K>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                        const float* __restrict__ stats, int nb,
                                                        const float* __restrict__ gscale_dev, float gscale,
                                                        float* __restrict__ dpred, float* __restrict__ loss_c, int64_t n,
-                                                       int64_t n4) {
+                                                       int64_t n4, K... kk) {
+    constexpr bool MASK = sizeof...(K) != 0;
+    const LossMask k = mask_arg(kk...);
     __shared__ float red[4];
     float C = 0.f;
     if constexpr (KIND == TULIP_LOSS_BERHU) {
         C = berhu_threshold(stats, nb, red);
         if (blockIdx.x == 0 && threadIdx.x == 0) loss_c[0] = C;
     }
-    const float g = (gscale_dev ? gscale_dev[0] : gscale) / (float)n;
+    float g;
+    if constexpr (MASK) {
+        __shared__ long long cred[4];
+        const int64_t nv = valid_count(k.counts, nb, cred);
+        if (blockIdx.x == 0 && threadIdx.x == 0) k.n_valid[0] = nv;
+        g = nv ? (gscale_dev ? gscale_dev[0] : gscale) / (float)nv : 0.f;
+    } else {
+        g = (gscale_dev ? gscale_dev[0] : gscale) / (float)n;
+    }
     const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
     for (int64_t i = first; i < n4; i += stride) {
         const float4 p = *(const float4*)(pred + i * 4), t = *(const float4*)(tgt + i * 4);
-        *(float4*)(dpred + i * 4) = make_float4(loss_grad<KIND>(p.x, t.x, C, g), loss_grad<KIND>(p.y, t.y, C, g),
-                                                loss_grad<KIND>(p.z, t.z, C, g), loss_grad<KIND>(p.w, t.w, C, g));
+        float4 d = make_float4(loss_grad<KIND>(p.x, t.x, C, g), loss_grad<KIND>(p.y, t.y, C, g),
+                               loss_grad<KIND>(p.z, t.z, C, g), loss_grad<KIND>(p.w, t.w, C, g));
+        if constexpr (MASK) {
+            const float4 z = mask_src4(tgt, i * 4, t, k);
+            d = make_float4(z.x > k.valid_min ? d.x : 0.f, z.y > k.valid_min ? d.y : 0.f, z.z > k.valid_min ? d.z : 0.f,
+                            z.w > k.valid_min ? d.w : 0.f);
+        }
+        *(float4*)(dpred + i * 4) = d;
     }
-    for (int64_t i = n4 * 4 + first; i < n; i += stride) dpred[i] = loss_grad<KIND>(pred[i], tgt[i], C, g);
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        const float d = loss_grad<KIND>(pred[i], tgt[i], C, g);
+        if constexpr (MASK) dpred[i] = mask_src(tgt, i, tgt[i], k) > k.valid_min ? d : 0.f;
+        else dpred[i] = d;
+    }
 }
 
-// berHu's second pass: vpart[wg] = the workgroup's sum of the elementwise values (the sum needs C)
+// berHu's second pass: vpart[wg] = the workgroup's sum of the elementwise values (the sum needs C); MASK: of the valid elements
+// (n_v == 0: nothing is read)
+template <class... K>
 __global__ __launch_bounds__(256) void loss_value_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                          const float* __restrict__ stats, int nb, float* __restrict__ vpart,
-                                                         int64_t n, int64_t n4) {
+                                                         int64_t n, int64_t n4, K... kk) {
+    constexpr bool MASK = sizeof...(K) != 0;
+    const LossMask k = mask_arg(kk...);
     __shared__ float red[4];
     __shared__ float sum[1][4];
+    if constexpr (MASK) {
+        __shared__ long long cred[4];
+        if (valid_count(k.counts, nb, cred) == 0) {       // (the same n_v in every thread: a uniform exit)
+            if (threadIdx.x == 0) vpart[blockIdx.x] = 0.f;
+            return;
+        }
+    }
     const float C = berhu_threshold(stats, nb, red);
     float s = 0.f;
     const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
     for (int64_t i = first; i < n4; i += stride) {
         const float4 p = *(const float4*)(pred + i * 4), t = *(const float4*)(tgt + i * 4);
-        s += berhu_value(p.x - t.x, C); s += berhu_value(p.y - t.y, C);
-        s += berhu_value(p.z - t.z, C); s += berhu_value(p.w - t.w, C);
+        if constexpr (MASK) {
+            const float4 z = mask_src4(tgt, i * 4, t, k);
+            if (z.x > k.valid_min) s += berhu_value(p.x - t.x, C);
+            if (z.y > k.valid_min) s += berhu_value(p.y - t.y, C);
+            if (z.z > k.valid_min) s += berhu_value(p.z - t.z, C);
+            if (z.w > k.valid_min) s += berhu_value(p.w - t.w, C);
+        } else {
+            s += berhu_value(p.x - t.x, C); s += berhu_value(p.y - t.y, C);
+            s += berhu_value(p.z - t.z, C); s += berhu_value(p.w - t.w, C);
+        }
     }
-    for (int64_t i = n4 * 4 + first; i < n; i += stride) s += berhu_value(pred[i] - tgt[i], C);
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        if constexpr (MASK) {
+            if (mask_src(tgt, i, tgt[i], k) > k.valid_min) s += berhu_value(pred[i] - tgt[i], C);
+        } else {
+            s += berhu_value(pred[i] - tgt[i], C);
+        }
+    }
     block_sum(s, sum, 0);
     __syncthreads();
     if (threadIdx.x == 0) vpart[blockIdx.x] = (sum[0][0] + sum[0][1]) + (sum[0][2] + sum[0][3]);
 }
 
-// one workgroup: the partials folded in double (l1_final_kernel's order); losses[0] = the chosen loss, losses[1] = pixel_loss
+// one workgroup: the partials folded in double (l1_final_kernel's order); losses[0] = the chosen loss, losses[1] = pixel_loss.
+// MASK: inv_n = 1 / n_v formed here from the counts (0 when n_v == 0: both losses 0), n_v written to k.n_valid
+template <class... K>
 __global__ __launch_bounds__(256) void loss_final_kernel(int kind, const float* __restrict__ stats,
                                                          const float* __restrict__ vpart, float* __restrict__ losses, int nb,
-                                                         double inv_n, int log_transform) {
+                                                         double inv_n, int log_transform, K... kk) {
+    constexpr bool MASK = sizeof...(K) != 0;
+    const LossMask k = mask_arg(kk...);
     __shared__ double red[3][4];
+    if constexpr (MASK) {
+        __shared__ long long cred[4];
+        const int64_t nv = valid_count(k.counts, nb, cred);
+        if (threadIdx.x == 0) k.n_valid[0] = nv;
+        inv_n = nv ? 1.0 / (double)nv : 0.0;
+    }
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) {
         s0 += stats[4 * i];
@@ -165,6 +299,87 @@ inline int64_t vec_groups(int64_t n, const void* a, const void* b, const void* c
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) ? 0 : n >> 2;
 }
 
+// the mask of an _m call, checked: false for what TULIP_ERR_ARG refuses.  (n < 2^41: a workgroup's count fits its uint32)
+inline bool make_mask(LossMask& k, int64_t n, int chans, int64_t chan_stride, float valid_min, const uint32_t* counts,
+                      int64_t* n_valid, bool wants_n_valid) {
+    if (chans < 1 || chan_stride < 1 || n <= 0 || n >= ((int64_t)1 << 41) || chan_stride > n / chans ||
+        n % (chans * chan_stride) != 0)
+        return false;
+    if (!(valid_min - valid_min == 0.f) || !counts || ((uintptr_t)counts & 3)) return false;       // NaN, infinities
+    if (wants_n_valid && (!n_valid || ((uintptr_t)n_valid & 7))) return false;
+    k = LossMask{chan_stride, chans, n < ((int64_t)1 << 32), valid_min, const_cast<uint32_t*>(counts), n_valid};
+    return true;
+}
+
+// the masked float4 route needs chan_stride % 4 == 0 besides the alignment (with target 16-byte aligned, its channel-0 rows then
+// are too): a group then never straddles a channel
+inline int64_t vec_groups_m(const LossMask* k, int64_t n, const void* a, const void* b, const void* c = nullptr) {
+    return (k && (k->chan_stride & 3)) ? 0 : vec_groups(n, a, b, c);
+}
+
+int launch_stats(const float* pred, const float* target, float* stats, int64_t n, int log_transform, const LossMask* k,
+                 hipStream_t stream) {
+    if (n <= 0 || !pred || !target || !stats || ((uintptr_t)stats & 15)) return TULIP_ERR_ARG;
+    const dim3 grid(tulip_loss_blocks(n)), block(256);
+    const int64_t n4 = vec_groups_m(k, n, pred, target);
+    if (k) hipLaunchKernelGGL(loss_stats_kernel<LossMask>, grid, block, 0, stream, pred, target, stats, n, n4, log_transform, *k);
+    else hipLaunchKernelGGL(loss_stats_kernel<>, grid, block, 0, stream, pred, target, stats, n, n4, log_transform);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+template <class... K>
+void launch_bwd_kind(int kind, dim3 grid, hipStream_t stream, const float* pred, const float* target, const float* stats, int nb,
+                     const float* gscale_dev, float gscale, float* dpred, float* loss_c, int64_t n, int64_t n4, K... k) {
+    const dim3 block(256);
+    if (kind == TULIP_LOSS_L1)
+        hipLaunchKernelGGL((loss_bwd_kernel<TULIP_LOSS_L1, K...>), grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale,
+                           dpred, loss_c, n, n4, k...);
+    else if (kind == TULIP_LOSS_L2)
+        hipLaunchKernelGGL((loss_bwd_kernel<TULIP_LOSS_L2, K...>), grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale,
+                           dpred, loss_c, n, n4, k...);
+    else
+        hipLaunchKernelGGL((loss_bwd_kernel<TULIP_LOSS_BERHU, K...>), grid, block, 0, stream, pred, target, stats, nb, gscale_dev,
+                           gscale, dpred, loss_c, n, n4, k...);
+}
+
+int launch_bwd(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev, float gscale,
+               float* dpred, float* loss_c, int64_t n, const LossMask* k, hipStream_t stream) {
+    if (bad_kind(kind) || n <= 0 || !pred || !target || !dpred) return TULIP_ERR_ARG;
+    if (kind == TULIP_LOSS_BERHU && (!stats || !loss_c)) return TULIP_ERR_ARG;
+    const int nb = tulip_loss_blocks(n);
+    const int64_t n4 = vec_groups_m(k, n, pred, target, dpred);
+    if (k) launch_bwd_kind(kind, dim3(nb), stream, pred, target, stats, nb, gscale_dev, gscale, dpred, loss_c, n, n4, *k);
+    else launch_bwd_kind(kind, dim3(nb), stream, pred, target, stats, nb, gscale_dev, gscale, dpred, loss_c, n, n4);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_value(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n, const LossMask* k,
+                 hipStream_t stream) {
+    if (n <= 0 || !pred || !target || !stats || !value_partials) return TULIP_ERR_ARG;
+    const int nb = tulip_loss_blocks(n);
+    const int64_t n4 = vec_groups_m(k, n, pred, target);
+    if (k) hipLaunchKernelGGL(loss_value_kernel<LossMask>, dim3(nb), dim3(256), 0, stream, pred, target, stats, nb, value_partials, n,
+                              n4, *k);
+    else hipLaunchKernelGGL(loss_value_kernel<>, dim3(nb), dim3(256), 0, stream, pred, target, stats, nb, value_partials, n, n4);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_final(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, int log_transform,
+                 const LossMask* k, hipStream_t stream) {
+    if (bad_kind(kind) || n <= 0 || !stats || !losses) return TULIP_ERR_ARG;
+    if (kind == TULIP_LOSS_BERHU && !value_partials) return TULIP_ERR_ARG;
+    const int nb = tulip_loss_blocks(n);
+    if (k) hipLaunchKernelGGL(loss_final_kernel<LossMask>, dim3(1), dim3(256), 0, stream, kind, stats, value_partials, losses, nb, 0.0,
+                              log_transform, *k);
+    else hipLaunchKernelGGL(loss_final_kernel<>, dim3(1), dim3(256), 0, stream, kind, stats, value_partials, losses, nb,
+                            1.0 / (double)n, log_transform);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
 }  // namespace
 
 extern "C" int tulip_loss_blocks(int64_t n) {
@@ -175,49 +390,50 @@ extern "C" int tulip_loss_blocks(int64_t n) {
 
 extern "C" int tulip_loss_stats(const float* pred, const float* target, float* stats, int64_t n, int log_transform,
                                 hipStream_t stream) {
-    if (n <= 0 || !pred || !target || !stats || ((uintptr_t)stats & 15)) return TULIP_ERR_ARG;
-    hipLaunchKernelGGL(loss_stats_kernel, dim3(tulip_loss_blocks(n)), dim3(256), 0, stream, pred, target, stats, n,
-                       vec_groups(n, pred, target), log_transform);
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return launch_stats(pred, target, stats, n, log_transform, nullptr, stream);
 }
 
 extern "C" int tulip_loss_bwd(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev,
                               float gscale, float* dpred, float* loss_c, int64_t n, hipStream_t stream) {
-    if (bad_kind(kind) || n <= 0 || !pred || !target || !dpred) return TULIP_ERR_ARG;
-    if (kind == TULIP_LOSS_BERHU && (!stats || !loss_c)) return TULIP_ERR_ARG;
-    const int nb = tulip_loss_blocks(n);
-    const int64_t n4 = vec_groups(n, pred, target, dpred);
-    const dim3 grid(nb), block(256);
-    if (kind == TULIP_LOSS_L1)
-        hipLaunchKernelGGL(loss_bwd_kernel<TULIP_LOSS_L1>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale, dpred,
-                           loss_c, n, n4);
-    else if (kind == TULIP_LOSS_L2)
-        hipLaunchKernelGGL(loss_bwd_kernel<TULIP_LOSS_L2>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale, dpred,
-                           loss_c, n, n4);
-    else
-        hipLaunchKernelGGL(loss_bwd_kernel<TULIP_LOSS_BERHU>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale,
-                           dpred, loss_c, n, n4);
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return launch_bwd(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n, nullptr, stream);
 }
 
 extern "C" int tulip_loss_value(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n,
                                 hipStream_t stream) {
-    if (n <= 0 || !pred || !target || !stats || !value_partials) return TULIP_ERR_ARG;
-    const int nb = tulip_loss_blocks(n);
-    hipLaunchKernelGGL(loss_value_kernel, dim3(nb), dim3(256), 0, stream, pred, target, stats, nb, value_partials, n,
-                       vec_groups(n, pred, target));
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return launch_value(pred, target, stats, value_partials, n, nullptr, stream);
 }
 
 extern "C" int tulip_loss_final(int kind, const float* stats, const float* value_partials, float* losses, int64_t n,
                                 int log_transform, hipStream_t stream) {
-    if (bad_kind(kind) || n <= 0 || !stats || !losses) return TULIP_ERR_ARG;
-    if (kind == TULIP_LOSS_BERHU && !value_partials) return TULIP_ERR_ARG;
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, stream, kind, stats, value_partials, losses, tulip_loss_blocks(n),
-                       1.0 / (double)n, log_transform);
-    TULIP_CHECK_LAUNCH();
-    return TULIP_OK;
+    return launch_final(kind, stats, value_partials, losses, n, log_transform, nullptr, stream);
+}
+
+// ---- the masked entry points: the same launches over the valid elements (LossMask above)
+extern "C" int tulip_loss_stats_m(const float* pred, const float* target, float* stats, int64_t n, int log_transform, int chans,
+                                  int64_t chan_stride, float valid_min, uint32_t* counts, hipStream_t stream) {
+    LossMask k;
+    if (!make_mask(k, n, chans, chan_stride, valid_min, counts, nullptr, false)) return TULIP_ERR_ARG;
+    return launch_stats(pred, target, stats, n, log_transform, &k, stream);
+}
+
+extern "C" int tulip_loss_bwd_m(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev,
+                                float gscale, float* dpred, float* loss_c, int64_t n, int chans, int64_t chan_stride,
+                                float valid_min, const uint32_t* counts, int64_t* n_valid, hipStream_t stream) {
+    LossMask k;
+    if (!make_mask(k, n, chans, chan_stride, valid_min, counts, n_valid, true)) return TULIP_ERR_ARG;
+    return launch_bwd(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n, &k, stream);
+}
+
+extern "C" int tulip_loss_value_m(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n,
+                                  int chans, int64_t chan_stride, float valid_min, const uint32_t* counts, hipStream_t stream) {
+    LossMask k;
+    if (!make_mask(k, n, chans, chan_stride, valid_min, counts, nullptr, false)) return TULIP_ERR_ARG;
+    return launch_value(pred, target, stats, value_partials, n, &k, stream);
+}
+
+extern "C" int tulip_loss_final_m(int kind, const float* stats, const float* value_partials, float* losses, int64_t n,
+                                  int log_transform, const uint32_t* counts, int64_t* n_valid, hipStream_t stream) {
+    LossMask k;
+    if (!make_mask(k, n, 1, 1, 0.f, counts, n_valid, true)) return TULIP_ERR_ARG;
+    return launch_final(kind, stats, value_partials, losses, n, log_transform, &k, stream);
 }

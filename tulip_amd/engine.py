@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib, knobs, ops
-from .loss import check_loss
+from .loss import check_loss, check_valid_min
 from ._lib import (EPI_BF16, EPI_F32, EPI_GELU_BWD, EPI_GELU_DUAL, EPI_PIXSHUF2_F32, EPI_RESID_F32,
                    EPI_UNSHUF2_BF16,
                    EPI_SPLIT_F32)
@@ -290,12 +290,17 @@ class Plan:
         self.partials = self.f32("partials", max(2048, 2 * ((B * H0 * W0 + 31) // 32)))   # loss partial sums (2 per block)
         self.gscale = self.f32("gscale", 1)
         self.gscale.fill_(1.0)
-        if eng.loss_kind != "l1":
+        if eng.loss_kind != "l1" or eng.loss_valid_min is not None:
             # TULIP(loss="l2" | "berhu") (tulip_amd/loss.py): the per-workgroup partials of tulip_loss_stats / tulip_loss_value and
             # berHu's threshold C = 0.2 max|pred - target| as the backward formed it (a device float, never read back by the step)
             self.loss_stats = self.f32("loss_stats", 4 * _lib.LOSS_BLOCKS_MAX).zero_()
             self.loss_vpart = self.f32("loss_vpart", _lib.LOSS_BLOCKS_MAX).zero_()
             self.loss_c = self.f32("loss_c", 1).zero_()
+        if eng.loss_valid_min is not None:
+            # TULIP(loss_valid_min=...), masked "l1" included: the valid elements tulip_loss_stats_m counted per workgroup (uint32
+            # on the device) and their sum n_v as the backward / the final fold formed it (a device int64, never read back)
+            self.loss_counts = self._alloc("loss_counts", (_lib.LOSS_BLOCKS_MAX,), torch.int32, dev).zero_()
+            self.loss_valid = self._alloc("loss_valid", (1,), torch.int64, dev).zero_()
         nslots = max(1, eng.n_drop_slots)
         self.drop_scale = self.f32("drop_scale", nslots, B)
         self.drop_scale.fill_(1.0)
@@ -1061,21 +1066,42 @@ class TulipEngine:
         """The model's training loss (TULIP(loss=...), tulip_amd/loss.py); "l1" for a model object without the attribute."""
         return check_loss(getattr(self.model, "loss", "l1"))
 
+    @property
+    def loss_valid_min(self) -> Optional[float]:
+        """The model's valid-pixel threshold (TULIP(loss_valid_min=...), tulip_amd/loss.py); None -- no mask -- for a model object
+        without the attribute."""
+        return check_valid_min(getattr(self.model, "loss_valid_min", None))
+
+    def _loss_mask(self, P: Plan) -> tuple:
+        """(chans, chan_stride, valid_min) of the masked launches on P.pred / P.target (B, in_chans, H, W)"""
+        return P.target.shape[1], P.target.shape[2] * P.target.shape[3], self.loss_valid_min
+
     def _loss_fwd(self, P: Plan, kind: str, defer: bool):
         """The loss read-out of a loss other than L1 behind the head's forward: tulip_loss_stats (berHu: at once -- its maxima are
         what the backward forms C from, on the device; L2: with the rest), then -- beside the chain when `defer` (run_backward
-        issues it; nothing on the GPU reads `losses`) -- berHu's value pass and the final fold."""
+        issues it; nothing on the GPU reads `losses`) -- berHu's value pass and the final fold.
+        With a mask (loss_valid_min; "l1" too) the masked launches, and the statistics at once for every kind: their counts are
+        what the backward forms n_v from."""
         n, lt = P.pred.numel(), self.model.log_transform
-        stats = lambda: ops.loss_stats(P.pred, P.target, P.loss_stats, n, lt)
-        if kind == "berhu":
-            stats()
+        if self.loss_valid_min is not None:
+            mask = self._loss_mask(P)
+            ops.loss_stats_m(P.pred, P.target, P.loss_stats, n, lt, *mask, P.loss_counts)
 
-        def fin():
+            def fin():
+                if kind == "berhu":
+                    ops.loss_value_m(P.pred, P.target, P.loss_stats, P.loss_vpart, n, *mask, P.loss_counts)
+                ops.loss_final_m(kind, P.loss_stats, P.loss_vpart, P.losses, n, lt, P.loss_counts, P.loss_valid)
+        else:
+            stats = lambda: ops.loss_stats(P.pred, P.target, P.loss_stats, n, lt)
             if kind == "berhu":
-                ops.loss_value(P.pred, P.target, P.loss_stats, P.loss_vpart, n)
-            else:
                 stats()
-            ops.loss_final(kind, P.loss_stats, P.loss_vpart, P.losses, n, lt)
+
+            def fin():
+                if kind == "berhu":
+                    ops.loss_value(P.pred, P.target, P.loss_stats, P.loss_vpart, n)
+                else:
+                    stats()
+                ops.loss_final(kind, P.loss_stats, P.loss_vpart, P.losses, n, lt)
         if defer:
             self._loss_final = fin
         else:
@@ -1189,7 +1215,8 @@ class TulipEngine:
         M0 = B * H0 * W0
         loss_done = False
         kind = self.loss_kind
-        l1 = with_loss and kind == "l1"            # the L1 partial sums ride in the head's forward; another loss reads pred behind it
+        # the L1 partial sums ride in the head's forward; another loss, and any loss over the valid pixels only, reads pred behind it
+        l1 = with_loss and kind == "l1" and self.loss_valid_min is None
         if m.pixel_shuffle and self.fuse_tail_fwd:
             # norm_up -> expand conv -> LeakyReLU -> PixelShuffle(4) -> decoder_pred (-> L1 partial sums) in ONE launch
             ops.tail_fwd_ln(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), self.eps, P["tail.xn"], P["tail.mean"],
@@ -1225,7 +1252,8 @@ class TulipEngine:
                                 pred=P.pred, in_chans=m.in_chans)
         self._join_pack()                          # (a model without fused wide blocks never asked for the copies)
         if with_loss and not loss_done and not l1:
-            self._loss_fwd(P, kind, False)
+            # (the masked read-out goes beside the chain with this head too)
+            self._loss_fwd(P, kind, defer_loss_final and self.loss_valid_min is not None)
         elif with_loss and not loss_done:
             ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform)
         P.generation += 1
@@ -1926,19 +1954,24 @@ class TulipEngine:
         M0 = B * H0 * W0
         gdw = G("decoder_pred.weight")
         kind = self.loss_kind
-        if kind != "l1":
+        l1 = kind == "l1" and self.loss_valid_min is None       # the head kernels form sign(pred - target) / n themselves
+        if self.loss_valid_min is not None:
+            # ... over the valid pixels (every kind, "l1" too): n_v from the forward's counts in this launch, +0 at the others
+            ops.loss_bwd_m(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel(),
+                           *self._loss_mask(P), P.loss_counts, P.loss_valid)
+        elif not l1:
             # d(loss)/d(pred) of the chosen loss in front of the head (csrc/loss.hip; berHu forms C from the forward's maxima in this
             # launch): the head kernels then take their `target == NULL` route -- dpred is the upstream gradient, gscale inside it
             ops.loss_bwd(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel())
         if m.pixel_shuffle:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
-            targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred if kind == "l1" else P.dpred)
+            targs = (P["tail.xn"], W_.p16(head_w), W_.p32(head_b), W_.p32("decoder_pred.weight"), P.pred if l1 else P.dpred)
             r = m.upscale_factor
             NE = r * r * E                              # output channels of the expand conv
             tkw = dict(target=P.target, gscale_dev=gscale_dev, gscale=gscale,   # L1 backward (tulip.py:692-693) formed in-kernel
                        in_chans=m.in_chans, r=r)
-            if kind != "l1":
+            if not l1:
                 tkw.update(target=None, gscale_dev=None, gscale=1.0)
             self._tail_fused = self.fuse_tail_bwd and ops.tail_fused_bwd_supported(E, r)
             if self._tail_fused:
@@ -1980,7 +2013,7 @@ class TulipEngine:
             r = m.upscale_factor
             NE = r * r * E
             pre = "final_patch_expanding"
-            if kind == "l1":
+            if l1:
                 ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
             R = ops.expand_norm_bwd_partial_rows(B, H0, W0, r)
             nrow = (2 + m.in_chans) * E                 # [dgamma | dbeta | d(decoder_pred.weight) (in_chans, E)]
@@ -2160,7 +2193,7 @@ class TulipEngine:
         # argument) and the number of draw slots
         key = key + (self.fuse_wide, self.fuse_wide_bwd, self.fuse_block96, self.fuse_block96_bwd, self.split_wide, self.split_wide_bwd,
                      self.fc1_grad_wide, self.fc1_grad96, self.recompute96, self.fuse_deep, self.fuse_tail_fwd, self.fuse_tail_bwd, self.fuse_glue, self.pair96, self.packed_gemm,
-                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind)
+                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind, self.loss_valid_min)
         ent = graphs.get(key)
         if not self.graph_module or ent is None:
             fn()

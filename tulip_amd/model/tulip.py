@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..loss import check_loss
+from ..loss import check_loss, check_valid_min
 
 __all__ = ["TULIP", "tulip_base", "tulip_large"]
 
@@ -173,22 +173,33 @@ class BasicBlockUp(_ParamHolder):  # tulip.py:441-475
 
 
 class TULIP(nn.Module):
-    """tulip.py:530-737.  Constructor signature and defaults are the reference's, followed by one keyword of this project's:
+    """tulip.py:530-737.  Constructor signature and defaults are the reference's, followed by two keywords of this project's:
 
     loss: "l1" (default: the reference's forward_loss, tulip.py:690-700), "l2" or "berhu" -- the training loss `forward` returns
     as total_loss and `loss.backward()` / Trainer differentiate (tulip_amd/loss.py is the definition; ValueError for another
     name).  berHu's threshold C = 0.2 max|pred - target| is formed on the device per call: per micro-batch under gradient
     accumulation and per rank with world > 1, as in the reference, where every rank computes its own loss.  pixel_loss, the third
-    value, stays the L1 metric for every kind.  Fixed at construction; state_dict() does not carry it."""
+    value, stays the L1 metric for every kind.  Fixed at construction; state_dict() does not carry it.
+
+    loss_valid_min: None (default: every pixel counts) or a finite float v, in the target's own units (behind log_transform; the
+    usual value is 0.0: FilterInvalidPixels writes the pixels without a return as 0 and log1p keeps them 0) -- the loss over the
+    valid pixels only.  Pixel (b, y, x) is valid iff target[b, 0, y, x] > v: channel 0, the range, decides for all in_chans
+    channels of the pixel (a valid return may have intensity 0), and a NaN there is not valid.  total_loss and pixel_loss are
+    the means over the n_v = in_chans * (valid pixels) valid elements, berHu's C the maximum over them, the gradient +0 at the
+    others; no valid pixel gives zeros.  A NaN or an infinity in the prediction or the target at an invalid pixel changes
+    nothing.  n_v is per call, as C is.  Fixed at construction; state_dict() does not carry it (ValueError for a bool, a NaN, an
+    infinity or another type)."""
 
     def __init__(self, img_size=(32, 2048), target_img_size=(128, 2048), patch_size=(4, 4), in_chans: int = 1,
                  embed_dim: int = 96, window_size=4, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
                  mlp_ratio: float = 4.0, qkv_bias: bool = True, drop_rate: float = 0.0, attn_drop_rate: float = 0.0,
                  drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True,
                  pixel_shuffle: bool = False, circular_padding: bool = False, swin_v2: bool = False,
-                 log_transform: bool = False, patch_unmerging: bool = False, loss: str = "l1"):
+                 log_transform: bool = False, patch_unmerging: bool = False, loss: str = "l1",
+                 loss_valid_min=None):
         super().__init__()
         self._loss = check_loss(loss)
+        self._loss_valid_min = check_valid_min(loss_valid_min)
         self.window_size = window_size
         self.depths, self.num_heads = tuple(depths), tuple(num_heads)
         self.num_layers = len(depths)
@@ -255,6 +266,11 @@ class TULIP(nn.Module):
     def loss(self) -> str:
         """the training loss chosen at construction (the engine's plans and captured graphs are built for it)"""
         return self._loss
+
+    @property
+    def loss_valid_min(self):
+        """the valid-pixel threshold of the loss chosen at construction: None (no mask) or a float (tulip_amd/loss.py)"""
+        return self._loss_valid_min
 
     # ------------------------------------------------------------------ engine plumbing
     def engine(self):

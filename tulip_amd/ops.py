@@ -404,6 +404,32 @@ def loss_final(kind, stats, value_partials, losses, n, log_transform):
                                        _stream()), "tulip_loss_final")
 
 
+def loss_stats_m(pred, target, stats, n, log_transform, chans, chan_stride, valid_min, counts):
+    """loss_stats over the valid elements (target[b, 0, pix] > valid_min; tulip_amd/loss.py), and counts (LOSS_BLOCKS_MAX uint32,
+    held in an int32 tensor): the valid elements per workgroup."""
+    check(_lib.load().tulip_loss_stats_m(_p(pred), _p(target), _p(stats), n, int(log_transform), int(chans), int(chan_stride),
+                                         float(valid_min), _p(counts), _stream()), "tulip_loss_stats_m")
+
+
+def loss_bwd_m(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n, chans, chan_stride, valid_min, counts, n_valid):
+    """loss_bwd with n_v = sum(counts) in place of n and +0 at the invalid elements; n_valid (one int64) receives n_v."""
+    check(_lib.load().tulip_loss_bwd_m(_loss_kind(kind), _p(pred), _p(target), _p(stats), _p(gscale_dev), float(gscale), _p(dpred),
+                                       _p(loss_c), n, int(chans), int(chan_stride), float(valid_min), _p(counts), _p(n_valid),
+                                       _stream()), "tulip_loss_bwd_m")
+
+
+def loss_value_m(pred, target, stats, value_partials, n, chans, chan_stride, valid_min, counts):
+    """berhu's second pass over the valid elements."""
+    check(_lib.load().tulip_loss_value_m(_p(pred), _p(target), _p(stats), _p(value_partials), n, int(chans), int(chan_stride),
+                                         float(valid_min), _p(counts), _stream()), "tulip_loss_value_m")
+
+
+def loss_final_m(kind, stats, value_partials, losses, n, log_transform, counts, n_valid):
+    """loss_final with 1 / n_v formed on the device from counts (both losses 0 when n_v == 0); n_valid receives n_v."""
+    check(_lib.load().tulip_loss_final_m(_loss_kind(kind), _p(stats), _p(value_partials), _p(losses), n, int(log_transform),
+                                         _p(counts), _p(n_valid), _stream()), "tulip_loss_final_m")
+
+
 def adamw(p, g, m, v, p_bf16, n, hyper, decay_mask64=None, zero_grad=False, lr_scale64=None, skip=None):
     """lr_scale64: per-group learning-rate scales (pack_lr_groups; tulip_adamw_s) -- None: tulip_adamw.
     skip: the non-finite guard's device flag (step_guard; tulip_adamw_g) -- None: the entry points without it."""

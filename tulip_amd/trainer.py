@@ -36,7 +36,7 @@ from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
 from .guard import check_skip_nonfinite
-from .loss import check_loss
+from .loss import check_loss, check_valid_min
 from .engine import ALIGN
 
 
@@ -118,11 +118,18 @@ class Trainer:
         that loss, `losses[1]` stays the L1 metric.  berHu's threshold C is formed on the device inside the captured graphs, per
         micro-batch under accum_iter > 1 and per rank with world > 1 (as in the reference, where every rank computes its own
         loss); `loss_c` is the device float of the last backward.  exchange="sharded" with a loss other than "l1" raises
-        ValueError (that plan is optional and unmeasured)."""
+        ValueError (that plan is optional and unmeasured).
+        The valid-pixel mask is the model's too (TULIP(loss_valid_min=...)): the loss, `losses[1]` and berHu's C are then over the
+        pixels whose target range exceeds the threshold, n_v of them counted on the device per micro-batch and per rank;
+        `loss_valid` is the device int64 of the last backward.  A NaN in a target pixel that the mask drops costs no step under
+        skip_nonfinite.  exchange="sharded" with a mask raises ValueError; state_dict() does not carry the setting."""
         skip_nonfinite = check_skip_nonfinite(skip_nonfinite)
         self.loss = check_loss(getattr(model, "loss", "l1"))
+        self.loss_valid_min = check_valid_min(getattr(model, "loss_valid_min", None))
         if self.loss != "l1" and exchange == "sharded":
             raise ValueError("exchange='sharded' with a loss other than 'l1' is not supported: use exchange='allreduce'")
+        if self.loss_valid_min is not None and exchange == "sharded":
+            raise ValueError("exchange='sharded' with loss_valid_min is not supported: use exchange='allreduce'")
         if skip_nonfinite and exchange == "sharded":
             raise ValueError("exchange='sharded' with skip_nonfinite is not supported (the per-bucket optimizer steps before the "
                              "global norm exists): use exchange='allreduce'")
@@ -348,6 +355,14 @@ class Trainer:
         if self.loss != "berhu":
             raise AttributeError("this Trainer's model has no berHu threshold: build the model with loss='berhu'")
         return self.P.loss_c
+
+    @property
+    def loss_valid(self) -> torch.Tensor:
+        """n_v, the valid elements (in_chans per valid pixel) of the last backward's loss: a device int64 (no sync); models built
+        with loss_valid_min only."""
+        if self.loss_valid_min is None:
+            raise AttributeError("this Trainer's model has no valid-pixel mask: build the model with loss_valid_min=...")
+        return self.P.loss_valid
 
     def _guard_word(self, k: int) -> int:
         if self._guard_state is None:

@@ -677,6 +677,33 @@ int tulip_range_prep(const void* raw, int raw_dtype, int64_t batch_stride, int64
                      int row_phase, int col_phase, float scale, int gate, float min_range, float max_range,
                      int log_transform, int roll_shift, hipStream_t stream);
 
+/* The same transforms with a per-sample augmentation drawn on the device from (seed, sample_ids[b]) and nothing else (host
+ * definition: tulip_amd/augment.py).  Arguments up to log_transform as above (no roll_shift); sample_ids: B device int64 words,
+ * read by the kernel, so a captured call replayed after the ids were rewritten in place draws for the new ids.
+ *   mix64 = the splitmix64 finaliser of "Element dropout";  K = mix64(seed ^ 0x52414E4745415547 ^ mix64(id));  draw(n) = mix64(K + n)
+ *   s    = ((draw(0) >> 32) * W) >> 32            in [0, W)            with TULIP_AUG_ROLL, else 0
+ *   flip = draw(1) >> 63                                               with TULIP_AUG_FLIP, else 0
+ *   p    = ((draw(2) >> 32) * row_factor) >> 32   in [0, row_factor)   with TULIP_AUG_ROW_PHASE, else row_phase
+ *   beam il dropped      iff (draw(2^20 + il) >> 40) < beam_threshold            (thresholds: rint(p * 2^24), at most 2^24)
+ *   point (il,jl) dropped iff (draw(2^32 + il*(W/col_factor) + jl) >> 40) < point_threshold
+ * The scan is mirrored, then rotated, and the pair is taken from it afterwards: with v0(i,j) the value tulip_range_prep forms
+ * for pixel (i,j) (the kernels share that expression: the outputs are bit for bit this gather of the plain outputs),
+ * c = (j - s) mod W and src(j) = flip ? W-1-c : c,
+ *   hi[i][j]   = v0(i, src(j))
+ *   lo[il][jl] = dropped ? +0.0f : v0(p + row_factor*il, src(col_phase + col_factor*jl))          (the target is never dropped)
+ * so any s is legal when the widths differ.  Every thread owns output pixels: stores are the plain call's aligned, coalesced
+ * ones for every draw, reads stay along the source's unit-stride axis.  params_out (B,4) int32 {s, flip, p, 0} per sample, or NULL.
+ * One launch, nothing allocated, no host state, graph-capturable.  TULIP_ERR_ARG before any launch: whatever tulip_range_prep
+ * refuses, sample_ids NULL or not 8-byte aligned, flag bits other than the three below, a threshold above 2^24. */
+#define TULIP_AUG_ROLL 1
+#define TULIP_AUG_FLIP 2
+#define TULIP_AUG_ROW_PHASE 4
+int tulip_range_prep_aug(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride, int64_t col_stride,
+                         int64_t base_offset, float* hi, float* lo, int B, int H, int W, int row_factor, int col_factor,
+                         int row_phase, int col_phase, float scale, int gate, float min_range, float max_range,
+                         int log_transform, const int64_t* sample_ids, uint64_t seed, int flags, uint32_t beam_threshold,
+                         uint32_t point_threshold, int32_t* params_out, hipStream_t stream);
+
 /* ---- evaluation post-processing and 3-D metrics (engine_upsampling.py:126-355,361-608; util/evaluation.py) ---- */
 
 /* MC-dropout aggregate (engine_upsampling.py:421-426): preds (passes, n) -> out (n):

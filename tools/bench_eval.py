@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Measurements for the 8(f) rows around the hot path (run on the GPU box):
   prep     : tulip_range_prep, KITTI B=8 from the interleaved .npy payload -> GB/s against the HBM roofline
+  prep_aug : tulip_range_prep_aug on the same two workloads (roll + flip + row phase, beam_drop 0.1, point_drop 0.05), timed in
+             alternation with the plain launch: per-pair ratio and its spread over the repeats; `--only prep` runs just these
   infer    : eval forward, tulip_base KITTI B=8, HIP-graph replay -> images/s (the MCdrop tile)
   evaluate : per-image post-processing + projection + voxel metrics + Chamfer -> ms/image, Chamfer pair rate
              against the fp32 vector-ALU rate, and the oracle (numpy/torch CPU) timed on the same image
@@ -30,6 +32,26 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
+def paired(fn_a, fn_b, iters, reps):
+    """fn_a and fn_b timed in alternating blocks of `iters` calls, `reps` times: (ms_a, ms_b) lists, one pair per repeat"""
+    a, b = [], []
+    timed(fn_a, iters)
+    timed(fn_b, iters)
+    for _ in range(reps):
+        a.append(timed(fn_a, iters, warm=1))
+        b.append(timed(fn_b, iters, warm=1))
+    return a, b
+
+
+def pair_record(workload, a, b, algo_bytes):
+    ratio = sorted(y / x for x, y in zip(a, b))
+    med = lambda v: sorted(v)[len(v) // 2]
+    return {"workload": workload, "plain_ms": med(a), "plain_ms_min_max": [min(a), max(a)], "ms": med(b),
+            "ms_min_max": [min(b), max(b)], "algorithmic_GBps": algo_bytes / med(b) / 1e6,
+            "plain_algorithmic_GBps": algo_bytes / med(a) / 1e6, "ratio_aug_over_plain": med(ratio),
+            "ratio_min_max": [ratio[0], ratio[-1]], "pairs": len(a)}
+
+
 def main():
     from tulip_amd import data as D, evaluation as EV
     from tulip_amd.infer import GraphedForward
@@ -57,6 +79,30 @@ def main():
     ms = timed(lambda: prep_big(big), 50)
     out["prep_large"] = {"workload": "durlar B=64 128x2048", "ms": ms,
                          "algorithmic_GBps": 64 * 128 * 2048 * 4 * 2.25 / ms / 1e6}
+    # ---- prep with the per-sample augmentation, in alternation with the plain launch of the same run
+    from tulip_amd.augment import RangeAugment
+    full = dict(beam_drop=0.1, point_drop=0.05)
+    ids8 = torch.arange(1000, 1008, device=dev)
+    prep_a = D.RangePrep("kitti", (16, 1024), (64, 1024), True, augment=RangeAugment(seed=0, **full))
+    a, b = paired(lambda: prep(payload), lambda: prep_a(payload, sample_ids=ids8), 200, 7)
+    out["prep_aug"] = pair_record("kitti B=8 64x1024 from (H,W,2) payload, roll+flip+row_phase, beam 0.1, point 0.05", a, b, algo)
+    out["prep_aug"]["note"] = "launch-latency bound like prep: the ratio of prep_large_aug is the signal"
+    ids64 = torch.arange(2000, 2064, device=dev)
+    algo_big = 64 * 128 * 2048 * 4 * 2.25
+    prep_big_a = D.RangePrep("durlar", (32, 2048), (128, 2048), True, augment=RangeAugment(seed=0, **full))
+    a, b = paired(lambda: prep_big(big), lambda: prep_big_a(big, sample_ids=ids64), 50, 7)
+    out["prep_large_aug"] = pair_record("durlar B=64 128x2048, roll+flip+row_phase, beam 0.1, point 0.05", a, b, algo_big)
+    # which part costs what: one augmentation at a time against the same plain launch (the stores are the plain launch's aligned
+    # ones for every draw; a shift with s % 4 != 0 reads two aligned source groups per four pixels, a mirror reads in descending order)
+    for name, kw in (("none", dict(roll=False, flip=False, row_phase=False)), ("roll", dict(flip=False, row_phase=False)),
+                     ("flip", dict(roll=False, row_phase=False)), ("row_phase", dict(roll=False, flip=False)),
+                     ("drops", dict(roll=False, flip=False, row_phase=False, **full))):
+        pk = D.RangePrep("durlar", (32, 2048), (128, 2048), True, augment=RangeAugment(seed=0, **kw))
+        a, b = paired(lambda: prep_big(big), lambda: pk(big, sample_ids=ids64), 50, 5)
+        out[f"prep_large_aug_{name}_only"] = pair_record(f"durlar B=64 128x2048, {kw}", a, b, algo_big)
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "prep":
+        print(json.dumps(out, indent=1))
+        return
     # ---- inference
     m = tulip_base(img_size=(16, 1024), target_img_size=(64, 1024), patch_size=(1, 4), in_chans=1, window_size=(2, 8),
                    pixel_shuffle=True, circular_padding=True, log_transform=True, patch_unmerging=True).to(dev).eval()

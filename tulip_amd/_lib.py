@@ -89,7 +89,8 @@ GEMM_B_PACKED = 0x1000
 ROUTE_TILE, ROUTE_FULL, ROUTE_MID, ROUTE_STREAM = range(4)
 ROUTE_DEEP, ROUTE_A_TRANS, ROUTE_B_TRANS, ROUTE_FOLD, ROUTE_SPLITS_SHIFT = 0x10, 0x20, 0x40, 0x80, 8
 LOSS_L1, LOSS_L2, LOSS_BERHU, LOSS_BLOCKS_MAX = 0, 1, 2, 1024      # TULIP_LOSS_* of tulip_hip.h
-ABI_VERSION = 6      # TULIP_ABI_VERSION of include/tulip_hip.h: the ctypes structs above mirror that layout
+AUG_ROLL, AUG_FLIP, AUG_ROW_PHASE = 1, 2, 4      # TULIP_AUG_* of tulip_hip.h
+ABI_VERSION = 6     # TULIP_ABI_VERSION of include/tulip_hip.h: the ctypes structs above mirror that layout
 
 # name -> argtypes (must mirror include/tulip_hip.h; tests/test_cabi.py cross-checks against the header)
 SIGNATURES = {
@@ -211,6 +212,9 @@ SIGNATURES = {
     "tulip_grad_clip": [P, L, P, P, P, P, P],
     "tulip_kitti_range_map": [P, L, I, I, F, F, F, F, F, P, P, P],
     "tulip_range_prep": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, I, P],
+    # ... with the per-sample augmentation: roll_shift -> sample_ids, seed, flags (AUG_* below), the two drop thresholds, params_out
+    "tulip_range_prep_aug": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, P, ctypes.c_uint64, I, ctypes.c_uint32,
+                             ctypes.c_uint32, P, P],
     "tulip_mc_aggregate": [P, I, L, F, P, P],
     "tulip_eval_postprocess": [P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "tulip_range_to_xyz": [P, P, P, P, P, F, I, I, P, P],

@@ -30,6 +30,15 @@ __device__ __forceinline__ float raw_to_float<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ float raw_to_float<__half>(__half v) { return __half2float(v); }
 
+// The value of one pixel; every kernel of this file, plain or augmented, forms it with this one expression, so an
+// augmented output is bit for bit a gather of the plain one.
+__device__ __forceinline__ float prep_value(float raw, const PrepArgs& a) {
+    float v = raw * a.scale;                                                                // ScaleTensor
+    if (a.gate) v = (v >= a.gmin && v <= a.gmax) ? v : 0.f;                                 // FilterInvalidPixels
+    if (a.logt) v = log1pf(v);                                                              // LogTransform
+    return v;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void range_prep_kernel(const T* __restrict__ raw, PrepArgs a) {
     __shared__ float tile[TI][TJ + 1];
@@ -44,9 +53,7 @@ __global__ __launch_bounds__(256) void range_prep_kernel(const T* __restrict__ r
         float v = 0.f;
         const bool need = a.hi || ((i - a.rp) % a.f == 0);
         if (i < a.H && j < a.W && need) {
-            v = raw_to_float<T>(src[(int64_t)i * a.si + (int64_t)j * a.sj]) * a.scale;   // ScaleTensor
-            if (a.gate) v = (v >= a.gmin && v <= a.gmax) ? v : 0.f;                        // FilterInvalidPixels
-            if (a.logt) v = log1pf(v);                                                      // LogTransform
+            v = prep_value(raw_to_float<T>(src[(int64_t)i * a.si + (int64_t)j * a.sj]), a);
         }
         tile[ii][jj] = v;
     }
@@ -95,12 +102,7 @@ __global__ __launch_bounds__(256) void range_prep_rows_kernel(const float* __res
             v[0] = q0.x; v[1] = q0.z; v[2] = q1.x; v[3] = q1.z;
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float x = v[c] * a.scale;
-            if (a.gate) x = (x >= a.gmin && x <= a.gmax) ? x : 0.f;
-            if (a.logt) x = log1pf(x);
-            v[c] = x;
-        }
+        for (int c = 0; c < 4; ++c) v[c] = prep_value(v[c], a);
         if (a.hi) {
             float* dst = a.hi + ((int64_t)b * a.H + i) * a.W;
             int jo = j + a.shift_hi;
@@ -133,7 +135,158 @@ __global__ __launch_bounds__(256) void range_prep_rows_kernel(const float* __res
     }
 }
 
-// ---- KITTI point cloud -> range image (kitti_utils/sample_kitti_dataset.py:24-66), float32 in numpy's op order
+// ---- per-sample augmentation (tulip_range_prep_aug; host definition tulip_amd/augment.py) -------------------------------
+// Gather formulation: a thread owns OUTPUT pixels, so every store is the plain kernels' aligned, coalesced one whatever the
+// sample drew; the rotation and the mirror only move where the (read-only, cache-served) source is read.  All draws come from
+// (seed, sample_ids[b]) with the counter-based generator of the dropout masks: key = mix64(seed ^ DOMAIN ^ mix64(id)),
+// draw(n) = mix64(key + n).
+struct AugArgs {
+    const long long* ids;
+    unsigned long long seed;
+    int flags;
+    uint32_t beam_thr, point_thr;
+    int32_t* params;
+};
+struct AugDraw {
+    uint64_t key;
+    int s, flip, p;
+};
+constexpr uint64_t AUG_DOMAIN = 0x52414E4745415547ull, AUG_BEAM = 1ull << 20, AUG_POINT = 1ull << 32;
+
+__device__ __forceinline__ AugDraw aug_draw(const AugArgs& g, int b, const PrepArgs& a) {
+    AugDraw d;
+    d.key = drop_mix64(g.seed ^ AUG_DOMAIN ^ drop_mix64((uint64_t)g.ids[b]));
+    d.s = (g.flags & TULIP_AUG_ROLL) ? (int)(((drop_mix64(d.key) >> 32) * (uint64_t)a.W) >> 32) : 0;
+    d.flip = (g.flags & TULIP_AUG_FLIP) ? (int)(drop_mix64(d.key + 1) >> 63) : 0;
+    d.p = (g.flags & TULIP_AUG_ROW_PHASE) ? (int)(((drop_mix64(d.key + 2) >> 32) * (uint64_t)a.f) >> 32) : a.rp;
+    return d;
+}
+__device__ __forceinline__ void aug_write_params(const AugArgs& g, const AugDraw& d, int b) {
+    int32_t* q = g.params + (int64_t)b * 4;
+    q[0] = d.s; q[1] = d.flip; q[2] = d.p; q[3] = 0;
+}
+// the source column of output column j: the scan is mirrored, then rotated by s
+__device__ __forceinline__ int aug_src(int j, const AugDraw& d, int W) {
+    int c = j - d.s;
+    if (c < 0) c += W;
+    return d.flip ? W - 1 - c : c;
+}
+__device__ __forceinline__ bool aug_dropped(uint64_t key, uint64_t n, uint32_t thr) {
+    return thr && (uint32_t)(drop_mix64(key + n) >> 40) < thr;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void range_prep_aug_kernel(const T* __restrict__ raw, PrepArgs a, AugArgs g) {
+    __shared__ float tile[TI][TJ + 1];
+    const int b = blockIdx.z, i0 = blockIdx.y * TI, j0 = blockIdx.x * TJ, t = threadIdx.x;
+    const AugDraw d = aug_draw(g, b, a);
+    if (g.params && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) aug_write_params(g, d, b);
+    const T* src = raw + (int64_t)b * a.sb + a.base;
+#pragma unroll
+    for (int k = 0; k < TI * TJ / 256; ++k) {
+        // fast thread index along the source's unit-stride axis; the tile's columns are OUTPUT columns, read at their sources
+        // (an ascending or descending run of source columns with at most one wrap)
+        const int ii = a.along_i ? (t & (TI - 1)) : (t / TJ + k * (256 / TJ));
+        const int jj = a.along_i ? (t / TI + k * (256 / TI)) : (t & (TJ - 1));
+        const int i = i0 + ii, j = j0 + jj;
+        float v = 0.f;
+        const bool need = a.hi || (i >= d.p && (i - d.p) % a.f == 0);
+        if (i < a.H && j < a.W && need)
+            v = prep_value(raw_to_float<T>(src[(int64_t)i * a.si + (int64_t)aug_src(j, d, a.W) * a.sj]), a);
+        tile[ii][jj] = v;
+    }
+    __syncthreads();
+    const int Hl = a.H / a.f, Wl = a.W / a.fw;
+#pragma unroll
+    for (int k = 0; k < TI * TJ / 256; ++k) {
+        const int ii = t / TJ + k * (256 / TJ), jj = t & (TJ - 1);
+        const int i = i0 + ii, j = j0 + jj;
+        if (i >= a.H || j >= a.W) continue;
+        const float v = tile[ii][jj];
+        if (a.hi) a.hi[((int64_t)b * a.H + i) * a.W + j] = v;
+        if (a.lo && i >= d.p && j >= a.cp && (i - d.p) % a.f == 0 && (j - a.cp) % a.fw == 0) {
+            const int il = (i - d.p) / a.f, jl = (j - a.cp) / a.fw;
+            const bool drop = aug_dropped(d.key, AUG_BEAM + (uint64_t)il, g.beam_thr) ||
+                              aug_dropped(d.key, AUG_POINT + (uint64_t)il * Wl + jl, g.point_thr);
+            if (il < Hl && jl < Wl) a.lo[((int64_t)b * Hl + il) * Wl + jl] = drop ? 0.f : v;
+        }
+    }
+}
+
+// 4 consecutive pixels of a row-major float32 row from the 16-byte aligned group at pixel g4 (a multiple of 4)
+template <int SJ>
+__device__ __forceinline__ void load_group4(const float* __restrict__ row, int g4, float* e) {
+    const float* p = row + (int64_t)g4 * SJ;
+    if (SJ == 1) {
+        const float4 q = *(const float4*)p;
+        e[0] = q.x; e[1] = q.y; e[2] = q.z; e[3] = q.w;
+    } else {
+        const float4 q0 = *(const float4*)p, q1 = *(const float4*)(p + 4);
+        e[0] = q0.x; e[1] = q0.z; e[2] = q1.x; e[3] = q1.z;
+    }
+}
+
+// Row-major float32 sources: a thread owns 4 consecutive OUTPUT pixels of one row (one 16-byte store to hi, one to lo when the
+// widths agree).  Their sources are 4 consecutive pixels (mod W), descending under a mirror; they start at a0 with a0 % 4 ==
+// (-s) % 4 either way, so a sample whose shift is a multiple of 4 reads one aligned group like the plain kernel and any other
+// sample reads the two aligned groups around them (the second one is its neighbour's first: served by the cache).
+template <int SJ>
+__global__ __launch_bounds__(256) void range_prep_rows_aug_kernel(const float* __restrict__ raw, PrepArgs a, AugArgs g) {
+    const int W4 = a.W >> 2;
+    const int64_t n4 = (int64_t)a.H * W4;
+    const int b = blockIdx.y;
+    const int Hl = a.H / a.f, Wl = a.W / a.fw;
+    const AugDraw d = aug_draw(g, b, a);
+    if (g.params && blockIdx.x == 0 && threadIdx.x == 0) aug_write_params(g, d, b);
+    const float* src = raw + (int64_t)b * a.sb;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n4; k += (int64_t)gridDim.x * 256) {
+        const int i = (int)(k / W4), j = (int)(k - (int64_t)i * W4) * 4;
+        const bool lo_row = a.lo && i >= d.p && (i - d.p) % a.f == 0;
+        if (!a.hi && !lo_row) continue;
+        int c = j - d.s;
+        if (c < 0) c += a.W;
+        int a0 = d.flip ? a.W - 4 - c : c;                  // the lowest of the 4 source pixels (mod W)
+        if (a0 < 0) a0 += a.W;
+        const int r = a0 & 3, g0 = a0 - r;
+        const float* row = src + (int64_t)i * a.si;
+        float e[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        load_group4<SJ>(row, g0, e);
+        if (r) load_group4<SJ>(row, g0 + 4 == a.W ? 0 : g0 + 4, e + 4);
+        float u[4], v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u[q] = r == 0 ? e[q] : r == 1 ? e[q + 1] : r == 2 ? e[q + 2] : e[q + 3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = prep_value(d.flip ? u[3 - q] : u[q], a);
+        if (a.hi) *(float4*)(a.hi + ((int64_t)b * a.H + i) * a.W + j) = make_float4(v[0], v[1], v[2], v[3]);
+        if (lo_row) {
+            const int il = (i - d.p) / a.f;
+            if (il >= Hl) continue;
+            float* dst = a.lo + ((int64_t)b * Hl + il) * Wl;
+            const bool beam = aug_dropped(d.key, AUG_BEAM + (uint64_t)il, g.beam_thr);
+            if (a.fw == 1) {
+                float w[4];         // a select into a fresh array: as `if (drop) v[q] = 0.f` the compiled kernel kept the point-dropped values
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool drop = beam || aug_dropped(d.key, AUG_POINT + (uint64_t)il * Wl + (j + q), g.point_thr);
+                    w[q] = drop ? 0.f : v[q];
+                }
+                *(float4*)(dst + j) = make_float4(w[0], w[1], w[2], w[3]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int jj = j + q;
+                    if (jj >= a.cp && (jj - a.cp) % a.fw == 0) {
+                        const int jl = (jj - a.cp) / a.fw;
+                        const bool drop = beam || aug_dropped(d.key, AUG_POINT + (uint64_t)il * Wl + jl, g.point_thr);
+                        dst[jl] = drop ? 0.f : v[q];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- KITTI point cloud -> range image(kitti_utils/sample_kitti_dataset.py:24-66), float32 in numpy's op order
 struct KittiProj {
     int rows, cols;
     float ang_start_y, ang_res_y, ang_res_x, max_range, min_range, half_cols;
@@ -181,18 +334,16 @@ __global__ __launch_bounds__(256) void kitti_resolve_kernel(const float* __restr
 
 inline int64_t iabs64(int64_t v) { return v < 0 ? -v : v; }
 
-}  // namespace
-
-extern "C" int tulip_range_prep(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride,
-                                int64_t col_stride, int64_t base_offset, float* hi, float* lo, int B, int H, int W,
-                                int row_factor, int col_factor, int row_phase, int col_phase, float scale, int gate,
-                                float min_range, float max_range, int log_transform, int roll_shift,
-                                hipStream_t stream) {
-    if (!raw || (!hi && !lo) || B <= 0 || H <= 0 || W <= 0 || row_factor < 1 || col_factor < 1) return TULIP_ERR_ARG;
+// The argument checks and the kernel arguments both entry points share; false: TULIP_ERR_ARG.  rows16: the source is row-major
+// float32 and everything is aligned for the 16-byte kernels.
+bool prep_setup(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride, int64_t col_stride,
+                int64_t base_offset, float* hi, float* lo, int B, int H, int W, int row_factor, int col_factor, int row_phase,
+                int col_phase, float scale, int gate, float min_range, float max_range, int log_transform, int roll_shift,
+                PrepArgs& a, bool& rows16) {
+    if (!raw || (!hi && !lo) || B <= 0 || H <= 0 || W <= 0 || row_factor < 1 || col_factor < 1) return false;
     if (H % row_factor || W % col_factor || row_phase < 0 || row_phase >= row_factor || col_phase < 0 ||
         col_phase >= col_factor || (raw_dtype != 0 && raw_dtype != 1))
-        return TULIP_ERR_ARG;
-    PrepArgs a;
+        return false;
     a.sb = batch_stride; a.si = row_stride; a.sj = col_stride; a.base = base_offset;
     a.hi = hi; a.lo = lo;
     a.H = H; a.W = W; a.f = row_factor; a.fw = col_factor; a.rp = row_phase; a.cp = col_phase;
@@ -201,17 +352,35 @@ extern "C" int tulip_range_prep(const void* raw, int raw_dtype, int64_t batch_st
     a.shift_hi = ((roll_shift % W) + W) % W;
     a.shift_lo = ((roll_shift % Wl) + Wl) % Wl;
     a.along_i = iabs64(row_stride) < iabs64(col_stride);
-    const bool rows16 = raw_dtype == 0 && (W & 3) == 0 && base_offset == 0 && (col_stride == 1 || col_stride == 2) &&
-                        row_stride == (int64_t)W * col_stride && (batch_stride & 3) == 0 &&
-                        ((uintptr_t)raw & 15) == 0 && (!hi || ((uintptr_t)hi & 15) == 0) && (!lo || ((uintptr_t)lo & 15) == 0) &&
-                        (Wl & 3) == 0;
+    rows16 = raw_dtype == 0 && (W & 3) == 0 && base_offset == 0 && (col_stride == 1 || col_stride == 2) &&
+             row_stride == (int64_t)W * col_stride && (batch_stride & 3) == 0 &&
+             ((uintptr_t)raw & 15) == 0 && (!hi || ((uintptr_t)hi & 15) == 0) && (!lo || ((uintptr_t)lo & 15) == 0) &&
+             (Wl & 3) == 0;
+    return true;
+}
+inline int prep_rows_blocks(int H, int W) {
+    int64_t nb = ((int64_t)H * (W / 4) + 255) / 256;
+    return nb > 2048 ? 2048 : (int)nb;
+}
+
+}  // namespace
+
+extern "C" int tulip_range_prep(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride,
+                                int64_t col_stride, int64_t base_offset, float* hi, float* lo, int B, int H, int W,
+                                int row_factor, int col_factor, int row_phase, int col_phase, float scale, int gate,
+                                float min_range, float max_range, int log_transform, int roll_shift,
+                                hipStream_t stream) {
+    PrepArgs a;
+    bool rows16;
+    if (!prep_setup(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor, col_factor,
+                    row_phase, col_phase, scale, gate, min_range, max_range, log_transform, roll_shift, a, rows16))
+        return TULIP_ERR_ARG;
     if (rows16) {
-        int64_t nb = ((int64_t)H * (W / 4) + 255) / 256;
-        if (nb > 2048) nb = 2048;
+        const dim3 grid(prep_rows_blocks(H, W), B);
         if (col_stride == 1)
-            hipLaunchKernelGGL(range_prep_rows_kernel<1>, dim3((int)nb, B), dim3(256), 0, stream, (const float*)raw, a);
+            hipLaunchKernelGGL(range_prep_rows_kernel<1>, grid, dim3(256), 0, stream, (const float*)raw, a);
         else
-            hipLaunchKernelGGL(range_prep_rows_kernel<2>, dim3((int)nb, B), dim3(256), 0, stream, (const float*)raw, a);
+            hipLaunchKernelGGL(range_prep_rows_kernel<2>, grid, dim3(256), 0, stream, (const float*)raw, a);
         TULIP_CHECK_LAUNCH();
         return TULIP_OK;
     }
@@ -220,6 +389,42 @@ extern "C" int tulip_range_prep(const void* raw, int raw_dtype, int64_t batch_st
         hipLaunchKernelGGL(range_prep_kernel<float>, grid, dim3(256), 0, stream, (const float*)raw, a);
     else
         hipLaunchKernelGGL(range_prep_kernel<__half>, grid, dim3(256), 0, stream, (const __half*)raw, a);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_range_prep_aug(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride,
+                                    int64_t col_stride, int64_t base_offset, float* hi, float* lo, int B, int H, int W,
+                                    int row_factor, int col_factor, int row_phase, int col_phase, float scale, int gate,
+                                    float min_range, float max_range, int log_transform, const int64_t* sample_ids,
+                                    uint64_t seed, int flags, uint32_t beam_threshold, uint32_t point_threshold,
+                                    int32_t* params_out, hipStream_t stream) {
+    PrepArgs a;
+    bool rows16;
+    if (!prep_setup(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor, col_factor,
+                    row_phase, col_phase, scale, gate, min_range, max_range, log_transform, 0, a, rows16))
+        return TULIP_ERR_ARG;
+    if (!sample_ids || ((uintptr_t)sample_ids & 7) || ((uintptr_t)params_out & 3) ||
+        (flags & ~(TULIP_AUG_ROLL | TULIP_AUG_FLIP | TULIP_AUG_ROW_PHASE)) || beam_threshold > (1u << 24) ||
+        point_threshold > (1u << 24))
+        return TULIP_ERR_ARG;
+    AugArgs g;
+    g.ids = (const long long*)sample_ids; g.seed = seed; g.flags = flags;
+    g.beam_thr = beam_threshold; g.point_thr = point_threshold; g.params = params_out;
+    if (rows16) {
+        const dim3 grid(prep_rows_blocks(H, W), B);
+        if (col_stride == 1)
+            hipLaunchKernelGGL(range_prep_rows_aug_kernel<1>, grid, dim3(256), 0, stream, (const float*)raw, a, g);
+        else
+            hipLaunchKernelGGL(range_prep_rows_aug_kernel<2>, grid, dim3(256), 0, stream, (const float*)raw, a, g);
+        TULIP_CHECK_LAUNCH();
+        return TULIP_OK;
+    }
+    const dim3 grid((W + TJ - 1) / TJ, (H + TI - 1) / TI, B);
+    if (raw_dtype == 0)
+        hipLaunchKernelGGL(range_prep_aug_kernel<float>, grid, dim3(256), 0, stream, (const float*)raw, a, g);
+    else
+        hipLaunchKernelGGL(range_prep_aug_kernel<__half>, grid, dim3(256), 0, stream, (const __half*)raw, a, g);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

@@ -7,7 +7,9 @@ LogTransform -> RandomRollRangeMap, :244-340) once for the low-res and once for 
 collates.  Here the host only reads file payloads into one pinned staging buffer; ONE kernel
 (csrc/prep.hip, tulip_range_prep) reads the raw payload in place (interleaved .npy channel 0, transposed
 + flipped float16 .rimg) and writes the model's (low_res, high_res) batch.  No CPU fallback: without the
-HIP library `RangePrep.__call__` raises.
+HIP library `RangePrep.__call__` raises.  `RangePrep(augment=RangeAugment(...))` makes that launch draw a
+rotation, a mirror, the start row and beam / point drops per sample from (seed, sample id)
+(tulip_range_prep_aug; tulip_amd/augment.py is the definition).
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .augment import RangeAugment
 
 NPY_EXTENSIONS = (".npy", ".rimg", ".bin")        # datasets.py:39
 
@@ -36,7 +39,7 @@ class RangePrep:
 
     def __init__(self, dataset_select: str, img_size_low_res: Sequence[int], img_size_high_res: Sequence[int],
                  log_transform: bool = False, roll_shift: Optional[int] = None, row_phase: int = 0,
-                 col_phase: int = 0):
+                 col_phase: int = 0, augment: Optional[RangeAugment] = None):
         if dataset_select not in DATASET_PREP:
             raise KeyError(dataset_select)          # generate_dataset: dataset_list[args.dataset_select] (datasets.py:49-51)
         self.scale, self.gate = DATASET_PREP[dataset_select]
@@ -50,24 +53,66 @@ class RangePrep:
         # RandomRollRangeMap draws ONE shift when the dataset is built (:100-104) and keeps it for the whole run
         self.roll_shift = 0 if roll_shift is None else int(roll_shift)
         self.row_phase, self.col_phase = row_phase, col_phase
+        # per-sample augmentation drawn in the kernel from (augment.seed, sample id): tulip_amd/augment.py.  None: the plain launch
+        if augment is not None:
+            if not isinstance(augment, RangeAugment):
+                raise ValueError("augment must be a RangeAugment or None")
+            if roll_shift is not None:          # with augment.roll the shift is drawn; without it the entry point has none
+                raise ValueError("roll_shift cannot be combined with augment: augment.roll draws the shift per sample")
+            if augment.row_phase and row_phase != 0:
+                raise ValueError("augment.row_phase draws the start row per sample: it cannot be combined with row_phase != 0")
+        self.augment = augment
 
     # -- raw layouts ---------------------------------------------------------------------------------
     def _run(self, raw: torch.Tensor, dtype_code: int, sb: int, si: int, sj: int, base: int, B: int,
-             want_hi: bool, want_lo: bool):
+             want_hi: bool, want_lo: bool, sample_ids=None, params_out=None):
+        ids = self._check_ids(sample_ids, B)        # ValueError before the device is touched
         if not raw.is_cuda:
             raise RuntimeError("tulip_amd.data.RangePrep runs on the GPU only (HIP kernel, no CPU fallback)")
         dev = raw.device
         hi = torch.empty(B, 1, self.H, self.W, dtype=torch.float32, device=dev) if want_hi else None
         lo = torch.empty(B, 1, self.h, self.w, dtype=torch.float32, device=dev) if want_lo else None
         gmin, gmax = self.gate if self.gate is not None else (0.0, 0.0)
+        if self.augment is not None:
+            aug = self.augment
+            if not torch.is_tensor(ids):
+                ids = torch.tensor(ids, dtype=torch.int64).to(dev)
+            elif ids.device != dev:
+                raise ValueError("sample_ids must be on the device of raw")
+            if params_out is not None and (params_out.dtype != torch.int32 or tuple(params_out.shape) != (B, 4) or
+                                           not params_out.is_contiguous() or params_out.device != dev):
+                raise ValueError("params_out must be a contiguous (B,4) int32 tensor on the device of raw")
+            ops.range_prep_aug(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
+                               self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform, ids,
+                               aug.seed, aug.flags, *aug.thresholds, params_out)
+            return lo, hi
         ops.range_prep(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
                        self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform,
                        self.roll_shift)
         return lo, hi
 
-    def __call__(self, raw: torch.Tensor, want_hi: bool = True, want_lo: bool = True):
+    def _check_ids(self, sample_ids, B: int):
+        """The sample ids of an augmented call: a device int64 tensor of B elements, or a host sequence of B ints (wrapped to
+        int64, uploaded by the call)."""
+        if self.augment is None:
+            if sample_ids is not None:
+                raise ValueError("sample_ids given, but this RangePrep has no augment")
+            return None
+        if sample_ids is None:
+            raise ValueError("RangePrep(augment=...) needs sample_ids: the draws are a function of (seed, sample id)")
+        if torch.is_tensor(sample_ids):
+            if sample_ids.dtype != torch.int64 or sample_ids.numel() != B or not sample_ids.is_contiguous():
+                raise ValueError(f"sample_ids must be a contiguous int64 tensor of {B} elements")
+            return sample_ids if sample_ids.is_cuda else sample_ids.reshape(-1).tolist()
+        ids = [((int(v) + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63) for v in sample_ids]
+        if len(ids) != B:
+            raise ValueError(f"{len(ids)} sample ids for a batch of {B}")
+        return ids
+
+    def __call__(self, raw: torch.Tensor, want_hi: bool = True, want_lo: bool = True, sample_ids=None, params_out=None):
         """raw: (B,H,W) float32 metres, or the (B,H,W,2) [range, intensity] payload of B .npy files
-        (channel 0 is read in place).  Returns (low_res (B,1,h,w), high_res (B,1,H,W))."""
+        (channel 0 is read in place).  Returns (low_res (B,1,h,w), high_res (B,1,H,W)).  With augment: sample_ids (B ids) and
+        optionally params_out, a (B,4) int32 device tensor that receives (s, flip, p, 0) per sample."""
         if raw.dtype != torch.float32 or not raw.is_contiguous():
             raise TypeError("raw must be a contiguous float32 tensor")
         if raw.dim() == 4:
@@ -80,9 +125,10 @@ class RangePrep:
             raise ValueError("raw must be (B,H,W) or (B,H,W,C)")
         if (H, W) != (self.H, self.W):
             raise ValueError(f"raw image is {H}x{W}, img_size_high_res is {self.H}x{self.W}")
-        return self._run(raw, 0, H * W * sj, W * sj, sj, 0, B, want_hi, want_lo)
+        return self._run(raw, 0, H * W * sj, W * sj, sj, 0, B, want_hi, want_lo, sample_ids, params_out)
 
-    def from_rimg(self, payload: torch.Tensor, want_hi: bool = True, want_lo: bool = True):
+    def from_rimg(self, payload: torch.Tensor, want_hi: bool = True, want_lo: bool = True, sample_ids=None,
+                  params_out=None):
         """payload: (B, s1, s0) float16, the bytes of B .rimg files after their (s0, s1) header.  The
         reference reshapes to (s1, s0), transposes and flips both axes (datasets.py:181-193): pixel (i,j)
         is payload[s1-1-j, s0-1-i], read in place through negative strides."""
@@ -91,7 +137,7 @@ class RangePrep:
         B, s1, s0 = payload.shape
         if (s0, s1) != (self.H, self.W):
             raise ValueError(f".rimg header says {s0}x{s1}, img_size_high_res is {self.H}x{self.W}")
-        return self._run(payload, 1, s0 * s1, -1, -s0, s0 * s1 - 1, B, want_hi, want_lo)
+        return self._run(payload, 1, s0 * s1, -1, -s0, s0 * s1 - 1, B, want_hi, want_lo, sample_ids, params_out)
 
 
 # -- file payloads (host I/O only: no arithmetic on the pixels) ------------------------------------------
@@ -136,6 +182,7 @@ class DeviceRangeLoader:
         self.shuffle, self.drop_last, self.seed, self.epoch = shuffle, drop_last, seed, 0
         self.rank, self.world = rank, world_size
         self._stages, self._events, self._turn = [None, None], [None, None], 0
+        self._id_stages = [None, None]
 
     def set_epoch(self, epoch: int):                # DistributedSampler.set_epoch (main:311)
         self.epoch = epoch
@@ -156,23 +203,34 @@ class DeviceRangeLoader:
         n = len(self._order())
         return n // self.B if self.drop_last else -(-n // self.B)
 
-    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
-        idx = self._order()
+    def batches(self) -> List[Tuple[List[int], List[int]]]:
+        """Pure host: this rank's batches of the current epoch as (file indices, sample ids).  A sample's id is
+        epoch * len(files) + file index: a function of the file and the epoch alone, so RangePrep(augment=...) draws the same
+        augmentation for it at any batch size, batch position, rank and world size, and set_epoch gives fresh draws."""
+        idx, n, out = self._order(), len(self.files), []
         for s in range(0, len(idx), self.B):
             chunk = idx[s:s + self.B]
             if len(chunk) < self.B and self.drop_last:
-                return
-            paths = [self.files[i] for i in chunk]
-            if paths[0].lower().endswith(".rimg"):
-                pays = [read_rimg_payload(p)[2] for p in paths]
-                yield self.prep.from_rimg(self._upload(pays, torch.float16))
-            else:
-                pays = [read_npy_payload(p) for p in paths]
-                yield self.prep(self._upload(pays, torch.float32))
+                break
+            out.append((chunk, [self.epoch * n + i for i in chunk]))
+        return out
 
-    def _upload(self, pays, dtype) -> torch.Tensor:
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        aug = getattr(self.prep, "augment", None) is not None
+        for chunk, ids in self.batches():
+            paths = [self.files[i] for i in chunk]
+            rimg = paths[0].lower().endswith(".rimg")
+            pays = [read_rimg_payload(p)[2] for p in paths] if rimg else [read_npy_payload(p) for p in paths]
+            dev = self._upload(pays, torch.float16 if rimg else torch.float32, ids if aug else None)
+            kw = {}
+            if aug:
+                dev, kw["sample_ids"] = dev
+            yield self.prep.from_rimg(dev, **kw) if rimg else self.prep(dev, **kw)
+
+    def _upload(self, pays, dtype, ids=None):
         """Stack payloads in one of two pinned staging buffers and start the H2D copy; a buffer is rewritten
-        only after the copy that last read it has completed."""
+        only after the copy that last read it has completed.  With ids: they ride in the same turn's pinned int64 buffer,
+        and the return value is (payload, ids) on the device."""
         k, n, shape = self._turn, len(pays), tuple(pays[0].shape)
         self._turn ^= 1
         st = self._stages[k]
@@ -184,6 +242,12 @@ class DeviceRangeLoader:
         for b, a in enumerate(pays):
             st[b].copy_(torch.from_numpy(a))
         dev = st[:n].to(self.device, non_blocking=True)
+        if ids is not None:
+            ist = self._id_stages[k]
+            if ist is None or ist.shape[0] < n:
+                ist = self._id_stages[k] = torch.empty(max(n, self.B), dtype=torch.int64).pin_memory()
+            ist[:n].copy_(torch.tensor(ids, dtype=torch.int64))
+            dev = (dev, ist[:n].to(self.device, non_blocking=True))
         self._events[k].record(torch.cuda.current_stream(self.device))
         return dev
 

@@ -481,6 +481,19 @@ def range_prep(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset
                                        int(roll_shift), _stream()), "tulip_range_prep")
 
 
+def range_prep_aug(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor,
+                   col_factor, row_phase, col_phase, scale, gate, min_range, max_range, log_transform, sample_ids, seed,
+                   flags, beam_threshold, point_threshold, params_out=None):
+    """tulip_range_prep_aug: the transforms of range_prep with the per-sample augmentation the kernel draws from (seed,
+    sample_ids[b]); sample_ids: B device int64 words, params_out: (B,4) device int32 or None (tulip_amd/augment.py is the host
+    definition)."""
+    check(_lib.load().tulip_range_prep_aug(_p(raw), raw_dtype, batch_stride, row_stride, col_stride, base_offset, _p(hi),
+                                           _p(lo), B, H, W, row_factor, col_factor, row_phase, col_phase, float(scale),
+                                           int(gate), float(min_range), float(max_range), int(log_transform),
+                                           _p(sample_ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), int(beam_threshold),
+                                           int(point_threshold), _p(params_out), _stream()), "tulip_range_prep_aug")
+
+
 # ---- evaluation post-processing / metrics (csrc/evalpost.hip)
 def mc_aggregate(preds, passes, n, noise_threshold, out):
     check(_lib.load().tulip_mc_aggregate(_p(preds), passes, n, float(noise_threshold), _p(out), _stream()),

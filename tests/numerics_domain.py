@@ -111,6 +111,20 @@ def round_bf16(r64, truncate=False) -> torch.Tensor:
 
 # ------------------------------------------------------------------ 1. / 2. GELU and GELU'
 GELU_E = 1e-6     # bound on the kernel's erf error: 1.5e-7 (Abramowitz-Stegun 7.1.26) + 6 roundings of terms <= 1.5 + 1 ulp of rcp
+# Relative error of a probability p = __expf(s - lse), lse = mx + __logf(sum), of the attention backward (tests/attn_exact.py),
+# per query row: lse is HELD in fp32, so it is off by up to ulp_f32(|lse|) (its own rounding, and the rounding of __logf(sum)
+# scaled down to it), and exp turns an absolute error of its argument into a relative one of p -- at |lse| ~ 256 that term is
+# 2^-15 and dominates; s - lse is exact or one rounding of a small number; the arguments that matter are -log n, small, where
+# __expf (v_exp_f32 of x log2 e) and __logf are good to a few ulp: 8 x 2^-24 for the two of them and the roundings between.
+# The same eps bounds the relative error of the row term delta = sum_key p dP against sum_key p |dP|: the common error of the p
+# goes through linearly, and the fp32 sum over L <= 64 keys adds L 2^-24 < 2^-18, which fits under the half of ulp_f32(lse) that
+# a round-to-nearest lse leaves unused.  (That holds for a delta summed over the keys; dO . O cancels across channels.)
+# A derivation from the number formats, never fitted to a kernel.
+ATTN_EXP_E = 8 * 2.0 ** -24
+
+
+def attn_p_eps(lse64):
+    return ulp_f32(lse64.abs()) + ATTN_EXP_E
 
 
 def all_finite_bf16() -> torch.Tensor:
@@ -436,14 +450,19 @@ def from_windows(t, B, H, W, win, sft):
 
 
 def attn_reference(qkv, table, B, H, W, C, nh, win, sft, masked, *, dtype=F64, softmax="exact", use_mask=True,
-                   shift_error=(0, 0), round_p=False):
+                   shift_error=(0, 0), round_p=False, p_mult=None, qk_cast=None):
     """The function documented above tulip_window_attn_fwd, in `dtype`: shift, partition, q * scale, + bias through the
     relative-position index, + 0 / -100 region mask, softmax, P.V, window reverse, reverse shift.  Returns (out [M][C],
-    scores [B nW][nh][L][L]).  The keyword switches build the deliberately wrong variants of the CPU tests."""
+    scores [B nW][nh][L][L]).  The keyword switches build the deliberately wrong variants of the CPU tests; p_mult
+    ([B nW][nh][L][L], the attn_drop multiplier on the probabilities, ahead of their rounding) and qk_cast (a dtype q and k are
+    rounded through: the fp8 scores) are the two documented options of the function."""
     L, P = win[0] * win[1], C // nh
     s_in = (sft[0] + shift_error[0], sft[1] + shift_error[1])
     t = to_windows(qkv.to(dtype), B, H, W, win, s_in).reshape(-1, L, 3, nh, P).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0] * P ** -0.5, t[1], t[2]
+    q, k, v = t[0], t[1], t[2]
+    if qk_cast is not None:
+        q, k = q.to(qk_cast).to(dtype), k.to(qk_cast).to(dtype)
+    q = q * P ** -0.5
     s = q @ k.transpose(-2, -1)
     s = s + table.to(dtype)[rel_position_index(*win).reshape(-1)].reshape(L, L, nh).permute(2, 0, 1)[None]
     if masked and use_mask:
@@ -455,6 +474,8 @@ def attn_reference(qkv, table, B, H, W, C, nh, win, sft, masked, *, dtype=F64, s
     else:                                           # no max subtraction
         e = torch.exp(s)
         p = e / e.sum(-1, keepdim=True)
+    if p_mult is not None:
+        p = p * p_mult.to(dtype)
     if round_p:
         p = p.to(torch.bfloat16).to(dtype)
     o = (p @ v).permute(0, 2, 1, 3).reshape(-1, L, C)

@@ -410,8 +410,10 @@ __global__ __launch_bounds__(64) void attn_fwd_wide_kernel(const bf16_t* __restr
 }
 
 // Backward, two phases per group of windows.  Phase A, lane = query: P from the recomputed scores, the row term
-// delta = dO . O (O recomputed from the (dropped) probabilities -- the same sum_key P * dP the 16-token kernel forms),
-// dS = P (dP - delta) and dQ = scale dS.K; dS and the (dropped) P stay in LDS ([item][query][key]).  Phase B, lane = key:
+// delta = sum_key P * dP with dP = (dO . V) * mask, summed as the 16-token kernel sums it (the algebraically equal dO . O
+// cancels across channels: its rounding error is not bounded by sum_key P |dP|, and a row whose dP are all 0 did not get 0),
+// dS = P (dP - delta) and dQ = scale dS.K; dS and the (dropped) P, rounded to bf16 as the forward rounds it ahead of P.V (and
+// as the 16-token kernel rounds its dV operand), stay in LDS ([item][query][key]).  Phase B, lane = key:
 // dK = scale dS^T.Q and dV = P^T.dO.  d(bias) leaves as one [L*L] partial row per workgroup, dbias_part[blockIdx.x][i*L+j]
 // (rows of one head nh apart): the workgroup owns its row and adds the dS of every trip to it (plain load / store, the
 // first trip stores; every group has at least one trip, wide_groups).
@@ -487,20 +489,18 @@ __global__ __launch_bounds__(64) void attn_bwd_wide_kernel(const bf16_t* __restr
         for (int k = 0; k < L; ++k) sum += __expf(dsr[k] - mx);
         const float lse = mx + __logf(sum);
         const uint64_t mb = (((uint64_t)win * g.nh + h) * L + s) * L;
-#pragma unroll
-        for (int d = 0; d < P; ++d) x[d] = 0.f;                     // x: O of the query row
+        float delta = 0.f;
 #pragma unroll 2
         for (int k = 0; k < L; ++k) {
             const float p = __expf(dsr[k] - lse);
             float pm = p;
             if constexpr (DROP) pm *= dropout_mul(dkey, mb + k, dthr, dscale);
             dsr[k] = p;
-            pmr[k] = valid ? pm : 0.f;
-            axpy_lds<P>(x, pm, Vw + k * ROW);
+            pmr[k] = valid ? round_bf16(pm) : 0.f;                  // dV takes the P the forward's P.V took
+            delta = fmaf(pm, dot_lds<P>(dor, Vw + k * ROW), delta);
         }
-        float delta = 0.f;
 #pragma unroll
-        for (int d = 0; d < P; ++d) { delta = fmaf(dor[d], x[d], delta); x[d] = 0.f; }   // x: dQ from here
+        for (int d = 0; d < P; ++d) x[d] = 0.f;                     // x: dQ from here
 #pragma unroll 2
         for (int k = 0; k < L; ++k) {
             float dp = dot_lds<P>(dor, Vw + k * ROW);

@@ -528,6 +528,44 @@ int tulip_loss_value_m(const float* pred, const float* target, const float* stat
 int tulip_loss_final_m(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, int log_transform,
                        const uint32_t* counts, int64_t* n_valid, hipStream_t stream);
 
+/* The edge term, TULIP(loss_edge_weight=w) (host definition: tulip_amd/loss.py): w * mean(|e_h| + |e_v|) beside the loss above,
+ * e_h / e_v the 3x3 Sobel responses of d = pred - target (the reference's util/filter.py, zero padding) on each of the `planes`
+ * = B * C planes of H x W on its own: nothing is read across a row end, a plane or a sample, and the columns do not wrap.
+ * fp32 order: e_h = ((d[+1,-1] - d[-1,-1]) + 2 (d[+1,0] - d[-1,0])) + (d[+1,+1] - d[-1,+1]) (d[dy,dx]), e_v the transposed
+ * pattern; sign(e) = (e > 0) - (e < 0), 0 for a NaN.  One workgroup of 256 threads per 8 x 128 tile, the tile and its halo
+ * staged in LDS, workgroup-strided over the tiles: tulip_loss_edge_blocks(planes, H, W) = min(TULIP_LOSS_BLOCKS_MAX, tiles)
+ * workgroups (host-only).  Fixed reduction orders, plain stores, no atomics, graph-capturable, 64-bit element offsets.
+ *   tulip_loss_edge_stats  edge_partials[wg] = the workgroup's sum of |e_h| + |e_v| (per thread, the wave tree, four wave results);
+ *                          edge_partials: TULIP_LOSS_BLOCKS_MAX floats
+ *   tulip_loss_edge_bwd    dpred[e] = fl32(dpred[e] + fl32(ge * k[e])) in place behind the base gradient, with
+ *                          g = fl32((gscale_dev ? gscale_dev[0] : gscale) / n) as in tulip_loss_bwd, ge = fl32(weight * g) and
+ *                          k[p,q] = sum_{i,j} K_h[i,j] sign(e_h[p-i+1,q-j+1]) + the same with K_v (an integer in [-16, 16];
+ *                          terms whose centre is outside the plane: 0).  A multiply, then an add: no fma
+ *   tulip_loss_edge_final  one workgroup behind the base loss's final launch: the partials folded in double,
+ *                          edge_out[0] = edge32 = fl32(sum / n), losses[0] = fl32(losses[0] + fl32(weight * edge32))
+ * The _m forms (TULIP(loss_valid_min=v)): pixel (b, y, x) is valid iff target[b, 0, y, x] > valid_min, plane p belonging to sample
+ * p / chans.  d is +0 at an invalid pixel (by selection: a NaN there reaches nothing), a response counts -- in the sum and in k --
+ * only where its centre is valid, n_v = the sum of the counts tulip_loss_stats_m wrote stands where n stands (n_v == 0: edge 0,
+ * gradient 0), and dpred is +0 at the invalid elements.
+ * TULIP_ERR_ARG before any launch: a non-positive planes / H / W (or n >= 2^41, H or W within 144 of INT_MAX, 2^31 or more
+ * tiles in one plane: the kernels' tile and pixel coordinates are 32-bit, only the element offsets 64-bit), a NULL pred / target / dpred / edge_partials /
+ * edge_out / losses, a misaligned edge_partials, a negative, NaN or infinite weight; _m: chans < 1, planes no multiple of chans,
+ * a NaN or infinite valid_min, a NULL or misaligned counts. */
+int tulip_loss_edge_blocks(int64_t planes, int H, int W);
+int tulip_loss_edge_stats(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
+                          hipStream_t stream);
+int tulip_loss_edge_bwd(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight, float* dpred,
+                        int64_t planes, int H, int W, hipStream_t stream);
+int tulip_loss_edge_final(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H, int W,
+                          hipStream_t stream);
+int tulip_loss_edge_stats_m(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W, int chans,
+                            float valid_min, hipStream_t stream);
+int tulip_loss_edge_bwd_m(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight,
+                          float* dpred, int64_t planes, int H, int W, int chans, float valid_min, const uint32_t* counts,
+                          hipStream_t stream);
+int tulip_loss_edge_final_m(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H, int W,
+                            const uint32_t* counts, hipStream_t stream);
+
 /* Fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, main_lidar_upsampling.py:283):
  * hyper (device, 8 floats) = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}.
  * decay_mask64[i/64] bit 0 selects weight decay for elements of 64-float block i/64 (timm's grouping,

@@ -187,6 +187,14 @@ SIGNATURES = {
     "tulip_loss_bwd_m": [I, P, P, P, P, F, P, P, L, I, L, F, P, P, P],
     "tulip_loss_value_m": [P, P, P, P, L, I, L, F, P, P],
     "tulip_loss_final_m": [I, P, P, P, L, I, P, P, P],
+    # the edge term (TULIP(loss_edge_weight=...)): planes = B * C planes of H x W; _m: + chans, valid_min (, counts)
+    "tulip_loss_edge_blocks": [L, I, I],
+    "tulip_loss_edge_stats": [P, P, P, L, I, I, P],
+    "tulip_loss_edge_bwd": [P, P, P, F, F, P, L, I, I, P],
+    "tulip_loss_edge_final": [P, P, P, F, L, I, I, P],
+    "tulip_loss_edge_stats_m": [P, P, P, L, I, I, I, F, P],
+    "tulip_loss_edge_bwd_m": [P, P, P, F, F, P, L, I, I, I, F, P, P],
+    "tulip_loss_edge_final_m": [P, P, P, F, L, I, I, P, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
     # ... and with a trailing-but-one lr_scale64 table: per-group learning-rate scales (group = mask byte >> 2)

@@ -380,6 +380,267 @@ int launch_final(int kind, const float* stats, const float* value_partials, floa
     return TULIP_OK;
 }
 
+// ---- the edge term, TULIP(loss_edge_weight=...) (tulip_amd/loss.py): the two 3x3 Sobel responses of d = pred - target per
+// (b, c) plane, zero outside the plane, and their adjoint for the gradient.  Not element-wise: one workgroup of 256 threads takes
+// one EDGE_TH x EDGE_TW tile of one plane (rows of 128 floats: coalesced along W), stages d for the tile plus its halo in LDS
+// (a few KB) and loops workgroup-strided over the remaining tiles.  Thread t owns column t & 127 and the four rows 4 (t >> 7) + r
+// of the tile.  Scalar loads and stores (the halo is unaligned anyway): one route whatever the pointers' alignment.
+constexpr int EDGE_TH = 8, EDGE_TW = 128;
+
+struct EdgeMask {
+    int chans;                 // plane p belongs to sample p / chans, whose channel-0 plane decides validity
+    float valid_min;
+};
+
+struct EdgeGeom {
+    int H, W, tiles_x, tiles_y;
+    int64_t tiles;             // planes * tiles_y * tiles_x
+};
+
+inline EdgeGeom edge_geom(int64_t planes, int H, int W) {
+    EdgeGeom g{H, W, (W + EDGE_TW - 1) / EDGE_TW, (H + EDGE_TH - 1) / EDGE_TH, 0};
+    g.tiles = planes * g.tiles_y * g.tiles_x;
+    return g;
+}
+
+// d of tile (plane, y0, x0) with a HALO-pixel border into sd, row pitch EDGE_TW + 2 HALO: pred - target inside the plane, +0
+// outside it -- the neighbouring row, plane and sample lie adjacent in memory and are never read for it -- and, MASK, +0 by
+// selection at an invalid pixel.  ok[i] = 1 where entry i is inside the plane (MASK: and valid).  64-bit element offsets.
+template <int HALO, bool MASK>
+__device__ __forceinline__ void edge_stage(float* sd, uint8_t* ok, const float* __restrict__ pred, const float* __restrict__ tgt,
+                                           int64_t plane, int y0, int x0, const EdgeGeom& g, const EdgeMask& k) {
+    constexpr int PW = EDGE_TW + 2 * HALO, PH = EDGE_TH + 2 * HALO;
+    const int64_t hw = (int64_t)g.H * g.W, base = plane * hw;
+    int64_t base0 = base;
+    if constexpr (MASK) base0 = (plane / k.chans) * k.chans * hw;
+    for (int i = threadIdx.x; i < PW * PH; i += 256) {
+        const int ly = i / PW, lx = i - ly * PW;
+        const int gy = y0 + ly - HALO, gx = x0 + lx - HALO;
+        float d = 0.f;
+        uint8_t v = 0;
+        if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
+            const int64_t off = (int64_t)gy * g.W + gx;
+            if constexpr (MASK) v = tgt[base0 + off] > k.valid_min;
+            else v = 1;
+            if (v) d = pred[base + off] - tgt[base + off];
+        }
+        sd[i] = d;
+        ok[i] = v;
+    }
+}
+
+// the two responses centred on entry c of a staged tile of row pitch PW, in the fixed order of tulip_amd/loss.py (2 a is exact:
+// an fma contraction of 2 a + b rounds as the two operations do)
+template <int PW>
+__device__ __forceinline__ void edge_responses(const float* sd, int c, float& eh, float& ev) {
+    const float a = sd[c - PW - 1], b = sd[c - PW], cc = sd[c - PW + 1], l = sd[c - 1], r = sd[c + 1], e = sd[c + PW - 1],
+                f = sd[c + PW], h = sd[c + PW + 1];
+    eh = ((e - a) + 2.f * (f - b)) + (h - cc);
+    ev = ((cc - a) + 2.f * (r - l)) + (h - e);
+}
+
+// fl32(c + fl32(a * b)): a multiply, then an add -- two roundings, as tulip_amd/loss.py states them.  (__fmul_rn / __fadd_rn are
+// plain operators in HIP's headers and contract into an fma like any others; the pragma is what keeps them apart.)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return c + p;
+}
+
+__device__ __forceinline__ void edge_tile(int64_t t, const EdgeGeom& g, int64_t& plane, int& y0, int& x0) {
+    const int per = g.tiles_y * g.tiles_x;
+    plane = t / per;
+    const int r = (int)(t - plane * per), ty = r / g.tiles_x;
+    y0 = ty * EDGE_TH;
+    x0 = (r - ty * g.tiles_x) * EDGE_TW;
+}
+
+// edge_partials[wg] = the workgroup's sum of |e_h| + |e_v| over its tiles (MASK: over the responses centred on a valid pixel):
+// per thread over its tiles and rows in order, the wave tree, four wave results
+template <bool MASK>
+__global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                         float* __restrict__ edge_partials, EdgeGeom g, EdgeMask k) {
+    constexpr int PW = EDGE_TW + 2;
+    __shared__ float sd[(EDGE_TH + 2) * PW];
+    __shared__ uint8_t ok[(EDGE_TH + 2) * PW];
+    __shared__ float red[1][4];
+    const int col = threadIdx.x & (EDGE_TW - 1), row0 = (threadIdx.x >> 7) * 4;
+    float s = 0.f;
+    for (int64_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        int64_t plane;
+        int y0, x0;
+        edge_tile(t, g, plane, y0, x0);
+        edge_stage<1, MASK>(sd, ok, pred, tgt, plane, y0, x0, g, k);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = (row0 + r + 1) * PW + col + 1;
+            if (ok[c]) {                               // inside the plane (and valid)
+                float eh, ev;
+                edge_responses<PW>(sd, c, eh, ev);
+                s += fabsf(eh) + fabsf(ev);
+            }
+        }
+        __syncthreads();
+    }
+    block_sum(s, red, 0);
+    __syncthreads();
+    if (threadIdx.x == 0) edge_partials[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+}
+
+// dpred[e] = fl32(dpred[e] + fl32(ge * k[e])), ge = fl32(weight * g) with g the base gradient's fl32(gscale / n) (MASK: n_v folded
+// here from the counts; g = 0 when n_v == 0), k the adjoint taps over the two sign maps -- signs zeroed where their centre is
+// outside the plane (MASK: or invalid); a NaN response has sign 0.  MASK: +0 at the invalid elements.  Every thread reads and
+// writes its own elements of dpred only.
+template <bool MASK>
+__global__ __launch_bounds__(256) void edge_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                       const float* __restrict__ gscale_dev, float gscale, float weight,
+                                                       float* __restrict__ dpred, int64_t n, const uint32_t* __restrict__ counts,
+                                                       int nb_counts, EdgeGeom g, EdgeMask k) {
+    constexpr int PW2 = EDGE_TW + 4, PW1 = EDGE_TW + 2, N1 = (EDGE_TH + 2) * PW1;
+    __shared__ float sd[(EDGE_TH + 4) * PW2];
+    __shared__ uint8_t ok[(EDGE_TH + 4) * PW2];
+    __shared__ int8_t sh[N1], sv[N1];
+    float gg;
+    if constexpr (MASK) {
+        __shared__ long long cred[4];
+        const int64_t nv = valid_count(counts, nb_counts, cred);
+        gg = nv ? (gscale_dev ? gscale_dev[0] : gscale) / (float)nv : 0.f;
+    } else {
+        gg = (gscale_dev ? gscale_dev[0] : gscale) / (float)n;
+    }
+    const float ge = weight * gg;
+    const int col = threadIdx.x & (EDGE_TW - 1), row0 = (threadIdx.x >> 7) * 4;
+    const int64_t hw = (int64_t)g.H * g.W;
+    for (int64_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        int64_t plane;
+        int y0, x0;
+        edge_tile(t, g, plane, y0, x0);
+        edge_stage<2, MASK>(sd, ok, pred, tgt, plane, y0, x0, g, k);
+        __syncthreads();
+        for (int i = threadIdx.x; i < N1; i += 256) {
+            const int ly = i / PW1, lx = i - ly * PW1, c = (ly + 1) * PW2 + lx + 1;
+            int8_t a = 0, b = 0;
+            if (ok[c]) {
+                float eh, ev;
+                edge_responses<PW2>(sd, c, eh, ev);
+                a = (int8_t)((eh > 0.f) - (eh < 0.f));
+                b = (int8_t)((ev > 0.f) - (ev < 0.f));
+            }
+            sh[i] = a;
+            sv[i] = b;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int y = y0 + row0 + r, x = x0 + col;
+            if (y < g.H && x < g.W) {
+                const int c = (row0 + r + 1) * PW1 + col + 1;
+                const int kh = ((int)sh[c - PW1 + 1] + 2 * (int)sh[c - PW1] + (int)sh[c - PW1 - 1]) -
+                               ((int)sh[c + PW1 + 1] + 2 * (int)sh[c + PW1] + (int)sh[c + PW1 - 1]);
+                const int kv = ((int)sv[c + PW1 - 1] + 2 * (int)sv[c - 1] + (int)sv[c - PW1 - 1]) -
+                               ((int)sv[c + PW1 + 1] + 2 * (int)sv[c + 1] + (int)sv[c - PW1 + 1]);
+                const int64_t e = plane * hw + (int64_t)y * g.W + x;
+                float out = mul_then_add(ge, (float)(kh + kv), dpred[e]);
+                if constexpr (MASK) {
+                    if (!ok[(row0 + r + 2) * PW2 + col + 2]) out = 0.f;
+                }
+                dpred[e] = out;
+            }
+        }
+        __syncthreads();                               // the next tile's staging rewrites ok, which the taps above still read
+    }
+}
+
+// one workgroup: the partials folded in double (loss_final_kernel's order); edge_out[0] = edge32 = fl32(sum * inv_n) and
+// losses[0] = fl32(losses[0] + fl32(weight * edge32)) behind the base loss's final launch.  MASK: inv_n = 1 / n_v from the counts
+template <bool MASK>
+__global__ __launch_bounds__(256) void edge_final_kernel(const float* __restrict__ edge_partials, int nb, float* __restrict__ edge_out,
+                                                         float* __restrict__ losses, float weight, double inv_n,
+                                                         const uint32_t* __restrict__ counts, int nb_counts) {
+    __shared__ double red[4];
+    if constexpr (MASK) {
+        __shared__ long long cred[4];
+        const int64_t nv = valid_count(counts, nb_counts, cred);
+        inv_n = nv ? 1.0 / (double)nv : 0.0;
+    }
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) s += edge_partials[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float edge32 = (float)(((red[0] + red[1]) + (red[2] + red[3])) * inv_n);
+        edge_out[0] = edge32;
+        losses[0] = mul_then_add(weight, edge32, losses[0]);
+    }
+}
+
+inline bool bad_weight(float w) { return !(w >= 0.f) || !(w - w == 0.f); }       // negative, NaN, infinite
+
+// the geometry of an edge call, checked (n = planes * H * W < 2^41 as in make_mask: planes * tiles per plane then fits int64 too)
+inline bool make_edge(EdgeGeom& g, int64_t& n, int64_t planes, int H, int W) {
+    if (planes <= 0 || H <= 0 || W <= 0) return false;
+    if (planes > (((int64_t)1 << 41) - 1) / H / W) return false;
+    // the kernels' tile and pixel coordinates are 32-bit: the halo must not carry y0 + ly or x0 + lx past INT_MAX, and the
+    // tiles of one plane must be countable in an int
+    if (H > INT_MAX - 16 || W > INT_MAX - EDGE_TW - 16) return false;
+    if ((int64_t)((H + EDGE_TH - 1) / EDGE_TH) * ((W + EDGE_TW - 1) / EDGE_TW) >= ((int64_t)1 << 31)) return false;
+    n = planes * H * W;
+    g = edge_geom(planes, H, W);
+    return true;
+}
+
+inline bool make_edge_mask(EdgeMask& k, int64_t planes, int chans, float valid_min) {
+    if (chans < 1 || planes % chans != 0 || !(valid_min - valid_min == 0.f)) return false;
+    k = EdgeMask{chans, valid_min};
+    return true;
+}
+
+inline int edge_grid(const EdgeGeom& g) { return (int)(g.tiles > LOSS_BLOCKS ? LOSS_BLOCKS : g.tiles); }
+
+int launch_edge_stats(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
+                      const EdgeMask* k, hipStream_t stream) {
+    EdgeGeom g;
+    int64_t n;
+    if (!make_edge(g, n, planes, H, W) || !pred || !target || !edge_partials || ((uintptr_t)edge_partials & 3)) return TULIP_ERR_ARG;
+    const dim3 grid(edge_grid(g)), block(256);
+    if (k) hipLaunchKernelGGL(edge_stats_kernel<true>, grid, block, 0, stream, pred, target, edge_partials, g, *k);
+    else hipLaunchKernelGGL(edge_stats_kernel<false>, grid, block, 0, stream, pred, target, edge_partials, g, EdgeMask{1, 0.f});
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_edge_bwd(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight, float* dpred,
+                    int64_t planes, int H, int W, const EdgeMask* k, const uint32_t* counts, hipStream_t stream) {
+    EdgeGeom g;
+    int64_t n;
+    if (!make_edge(g, n, planes, H, W) || !pred || !target || !dpred || bad_weight(weight)) return TULIP_ERR_ARG;
+    if (k && (!counts || ((uintptr_t)counts & 3))) return TULIP_ERR_ARG;
+    const dim3 grid(edge_grid(g)), block(256);
+    if (k) hipLaunchKernelGGL(edge_bwd_kernel<true>, grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred, n, counts,
+                              tulip_loss_blocks(n), g, *k);
+    else hipLaunchKernelGGL(edge_bwd_kernel<false>, grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred, n,
+                            (const uint32_t*)nullptr, 0, g, EdgeMask{1, 0.f});
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_edge_final(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H, int W,
+                      bool masked, const uint32_t* counts, hipStream_t stream) {
+    EdgeGeom g;
+    int64_t n;
+    if (!make_edge(g, n, planes, H, W) || !edge_partials || ((uintptr_t)edge_partials & 3) || !edge_out || !losses || bad_weight(weight))
+        return TULIP_ERR_ARG;
+    if (masked && (!counts || ((uintptr_t)counts & 3))) return TULIP_ERR_ARG;
+    if (masked) hipLaunchKernelGGL(edge_final_kernel<true>, dim3(1), dim3(256), 0, stream, edge_partials, edge_grid(g), edge_out, losses,
+                                   weight, 0.0, counts, tulip_loss_blocks(n));
+    else hipLaunchKernelGGL(edge_final_kernel<false>, dim3(1), dim3(256), 0, stream, edge_partials, edge_grid(g), edge_out, losses,
+                            weight, 1.0 / (double)n, (const uint32_t*)nullptr, 0);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
 }  // namespace
 
 extern "C" int tulip_loss_blocks(int64_t n) {
@@ -436,4 +697,46 @@ extern "C" int tulip_loss_final_m(int kind, const float* stats, const float* val
     LossMask k;
     if (!make_mask(k, n, 1, 1, 0.f, counts, n_valid, true)) return TULIP_ERR_ARG;
     return launch_final(kind, stats, value_partials, losses, n, log_transform, &k, stream);
+}
+
+// ---- the edge term (TULIP(loss_edge_weight=...)): three launches behind the base loss's, each with a masked twin
+extern "C" int tulip_loss_edge_blocks(int64_t planes, int H, int W) {
+    EdgeGeom g;
+    int64_t n;
+    return make_edge(g, n, planes, H, W) ? edge_grid(g) : 0;
+}
+
+extern "C" int tulip_loss_edge_stats(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
+                                     hipStream_t stream) {
+    return launch_edge_stats(pred, target, edge_partials, planes, H, W, nullptr, stream);
+}
+
+extern "C" int tulip_loss_edge_bwd(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight,
+                                   float* dpred, int64_t planes, int H, int W, hipStream_t stream) {
+    return launch_edge_bwd(pred, target, gscale_dev, gscale, weight, dpred, planes, H, W, nullptr, nullptr, stream);
+}
+
+extern "C" int tulip_loss_edge_final(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H,
+                                     int W, hipStream_t stream) {
+    return launch_edge_final(edge_partials, edge_out, losses, weight, planes, H, W, false, nullptr, stream);
+}
+
+extern "C" int tulip_loss_edge_stats_m(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
+                                       int chans, float valid_min, hipStream_t stream) {
+    EdgeMask k;
+    if (!make_edge_mask(k, planes, chans, valid_min)) return TULIP_ERR_ARG;
+    return launch_edge_stats(pred, target, edge_partials, planes, H, W, &k, stream);
+}
+
+extern "C" int tulip_loss_edge_bwd_m(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight,
+                                     float* dpred, int64_t planes, int H, int W, int chans, float valid_min,
+                                     const uint32_t* counts, hipStream_t stream) {
+    EdgeMask k;
+    if (!make_edge_mask(k, planes, chans, valid_min)) return TULIP_ERR_ARG;
+    return launch_edge_bwd(pred, target, gscale_dev, gscale, weight, dpred, planes, H, W, &k, counts, stream);
+}
+
+extern "C" int tulip_loss_edge_final_m(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes,
+                                       int H, int W, const uint32_t* counts, hipStream_t stream) {
+    return launch_edge_final(edge_partials, edge_out, losses, weight, planes, H, W, true, counts, stream);
 }

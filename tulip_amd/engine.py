@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib, knobs, ops
-from .loss import check_loss, check_valid_min
+from .loss import check_edge_weight, check_loss, check_valid_min
 from ._lib import (EPI_BF16, EPI_F32, EPI_GELU_BWD, EPI_GELU_DUAL, EPI_PIXSHUF2_F32, EPI_RESID_F32,
                    EPI_UNSHUF2_BF16,
                    EPI_SPLIT_F32)
@@ -301,6 +301,11 @@ class Plan:
             # on the device) and their sum n_v as the backward / the final fold formed it (a device int64, never read back)
             self.loss_counts = self._alloc("loss_counts", (_lib.LOSS_BLOCKS_MAX,), torch.int32, dev).zero_()
             self.loss_valid = self._alloc("loss_valid", (1,), torch.int64, dev).zero_()
+        if eng.loss_edge_weight > 0.0:
+            # TULIP(loss_edge_weight=...): the per-workgroup sums of tulip_loss_edge_stats and the edge term as the final fold formed
+            # it (a device float, never read back by the step)
+            self.loss_edge_part = self.f32("loss_edge_part", _lib.LOSS_BLOCKS_MAX).zero_()
+            self.loss_edge = self.f32("loss_edge", 1).zero_()
         nslots = max(1, eng.n_drop_slots)
         self.drop_scale = self.f32("drop_scale", nslots, B)
         self.drop_scale.fill_(1.0)
@@ -1072,9 +1077,36 @@ class TulipEngine:
         without the attribute."""
         return check_valid_min(getattr(self.model, "loss_valid_min", None))
 
+    @property
+    def loss_edge_weight(self) -> float:
+        """The weight of the model's edge term (TULIP(loss_edge_weight=...), tulip_amd/loss.py); 0.0 -- no term -- for a model
+        object without the attribute."""
+        return check_edge_weight(getattr(self.model, "loss_edge_weight", 0.0))
+
     def _loss_mask(self, P: Plan) -> tuple:
         """(chans, chan_stride, valid_min) of the masked launches on P.pred / P.target (B, in_chans, H, W)"""
         return P.target.shape[1], P.target.shape[2] * P.target.shape[3], self.loss_valid_min
+
+    def _edge_args(self, P: Plan) -> tuple:
+        """((planes, H, W), {mask, counts}) of the tulip_loss_edge_* launches on P.pred / P.target"""
+        B, C, H, W = P.target.shape
+        if self.loss_valid_min is None:
+            return (B * C, H, W), {}
+        return (B * C, H, W), dict(mask=(C, self.loss_valid_min), counts=P.loss_counts)
+
+    def _with_edge(self, P: Plan, fin):
+        """`fin`, the base loss's final launch(es), with the edge term's read-out behind it on the same stream: tulip_loss_edge_stats,
+        then tulip_loss_edge_final, which adds weight * edge into the losses[0] `fin` wrote.  Weight 0: `fin` itself."""
+        w = self.loss_edge_weight
+        if w == 0.0:
+            return fin
+
+        def both():
+            fin()
+            dims, kw = self._edge_args(P)
+            ops.loss_edge_stats(P.pred, P.target, P.loss_edge_part, *dims, **kw)
+            ops.loss_edge_final(P.loss_edge_part, P.loss_edge, P.losses, w, *dims, **kw)
+        return both
 
     def _loss_fwd(self, P: Plan, kind: str, defer: bool):
         """The loss read-out of a loss other than L1 behind the head's forward: tulip_loss_stats (berHu: at once -- its maxima are
@@ -1102,6 +1134,7 @@ class TulipEngine:
                 else:
                     stats()
                 ops.loss_final(kind, P.loss_stats, P.loss_vpart, P.losses, n, lt)
+        fin = self._with_edge(P, fin)
         if defer:
             self._loss_final = fin
         else:
@@ -1227,7 +1260,8 @@ class TulipEngine:
             if with_loss and not l1:
                 self._loss_fwd(P, kind, defer_loss_final)
             elif with_loss:
-                fin = lambda: ops.l1_loss_final(P.partials, P.losses, (M0 + 31) // 32, P.pred.numel(), m.log_transform)
+                fin = self._with_edge(P, lambda: ops.l1_loss_final(P.partials, P.losses, (M0 + 31) // 32, P.pred.numel(),
+                                                                   m.log_transform))
                 if defer_loss_final:
                     self._loss_final = fin            # run_backward issues it beside the chain (nothing on the GPU reads it)
                 else:
@@ -1255,7 +1289,7 @@ class TulipEngine:
             # (the masked read-out goes beside the chain with this head too)
             self._loss_fwd(P, kind, defer_loss_final and self.loss_valid_min is not None)
         elif with_loss and not loss_done:
-            ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform)
+            self._with_edge(P, lambda: ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform))()
         P.generation += 1
         P.last_x = x
 
@@ -1954,8 +1988,14 @@ class TulipEngine:
         M0 = B * H0 * W0
         gdw = G("decoder_pred.weight")
         kind = self.loss_kind
-        l1 = kind == "l1" and self.loss_valid_min is None       # the head kernels form sign(pred - target) / n themselves
-        if self.loss_valid_min is not None:
+        edge_w = self.loss_edge_weight
+        # the head kernels form sign(pred - target) / n themselves -- unless the edge term has to be added to it: L1 then takes the
+        # dpred route of the other losses
+        l1 = kind == "l1" and self.loss_valid_min is None and edge_w == 0.0
+        l1_dpred = kind == "l1" and self.loss_valid_min is None and edge_w > 0.0
+        if l1_dpred:
+            ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
+        elif self.loss_valid_min is not None:
             # ... over the valid pixels (every kind, "l1" too): n_v from the forward's counts in this launch, +0 at the others
             ops.loss_bwd_m(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel(),
                            *self._loss_mask(P), P.loss_counts, P.loss_valid)
@@ -1963,6 +2003,10 @@ class TulipEngine:
             # d(loss)/d(pred) of the chosen loss in front of the head (csrc/loss.hip; berHu forms C from the forward's maxima in this
             # launch): the head kernels then take their `target == NULL` route -- dpred is the upstream gradient, gscale inside it
             ops.loss_bwd(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel())
+        if edge_w > 0.0:
+            # ... + weight * gscale * d(edge)/d(pred), added in place (csrc/loss.hip, tulip_loss_edge_bwd)
+            dims, ekw = self._edge_args(P)
+            ops.loss_edge_bwd(P.pred, P.target, gscale_dev, gscale, edge_w, P.dpred, *dims, **ekw)
         if m.pixel_shuffle:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
@@ -2193,7 +2237,8 @@ class TulipEngine:
         # argument) and the number of draw slots
         key = key + (self.fuse_wide, self.fuse_wide_bwd, self.fuse_block96, self.fuse_block96_bwd, self.split_wide, self.split_wide_bwd,
                      self.fc1_grad_wide, self.fc1_grad96, self.recompute96, self.fuse_deep, self.fuse_tail_fwd, self.fuse_tail_bwd, self.fuse_glue, self.pair96, self.packed_gemm,
-                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind, self.loss_valid_min)
+                     int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind, self.loss_valid_min,
+                     self.loss_edge_weight)
         ent = graphs.get(key)
         if not self.graph_module or ent is None:
             fn()

@@ -1,4 +1,4 @@
-"""The training loss, TULIP(loss="l1" | "l2" | "berhu") -- the host definition of what csrc/loss.hip computes on the device.
+"""The training loss, TULIP(loss="l1" | "l2" | "berhu", loss_edge_weight=w) -- the host definition of what csrc/loss.hip computes on the device.
 
 The reference's forward_loss is L1 (tulip.py:690-700), and that stays the default.  The alternative it imports and leaves unused
 (tulip.py:11, util/evaluation.py:177-180, inverse_huber_loss) is berHu, the usual depth-regression loss; L2 is its other half.
@@ -31,6 +31,30 @@ pixel_loss likewise.  The gradient at an invalid element is +0.  n_v == 0 gives 
 (a second departure from 0/0).  Whatever pred or any channel of target holds at an invalid pixel -- a NaN, an infinity -- changes
 nothing; a non-finite value at a valid element propagates as above.  n_v and C are per call.  valid_min=None (the default): every
 element counts, and each function returns what it returns without the keyword, bit for bit.
+
+The edge term, TULIP(loss_edge_weight=w) -- `edge_weight=w` below.  Every loss above is a per-pixel function of d; an upsampler
+smears depth discontinuities, and a gradient term beside the pixel loss is the usual remedy.  The reference ships the two filters
+(tulip.py:9 imports util/filter.py: HorizontalEdgeDetectionCNN and VerticalEdgeDetectionCNN, each a fixed 3x3 Sobel filter in a
+Conv2d(1, 1, 3, padding=1, bias=False)) and leaves them unused; the loss built from them is this project's.  With d (B, C, H, W):
+
+    K_h = [[-1,-2,-1],[0,0,0],[1,2,1]]     K_v = K_h transposed
+    e_h[b,c,y,x] = sum_{i,j in 0..2} K_h[i,j] d[b,c,y+i-1,x+j-1]      (0 outside the H x W plane, the conv's zero padding; every
+    e_v likewise with K_v                                              (b, c) plane on its own; the columns do not wrap)
+    edge  = (1/n) sum (|e_h| + |e_v|)
+    total = base(kind, valid_min) + w * edge                          (base: loss_value)
+    k[b,c,p,q] = sum_{i,j} K_h[i,j] sign(e_h[b,c,p-i+1,q-j+1]) + the same with K_v       (sign(0) = 0, the torch subgradient;
+    d total / d pred = base gradient + w * k / n                       terms whose centre is outside the plane: 0)
+
+k is an integer in [-16, 16].  With the mask: d is +0 at an invalid pixel (by selection: a NaN or an infinity there reaches
+nothing), a response counts only where its centre pixel is valid (and contributes 0 to k elsewhere), the normaliser is n_v
+(n_v == 0: edge 0, gradient 0) and the gradient at an invalid element stays +0.  pixel_loss does not change, log_transform plays
+no part, and the term is per rank and per micro-batch, as berHu's C is.  A NaN response contributes 0 to k and makes the edge sum,
+and the loss with it, NaN.  The device's float32 arithmetic (csrc/loss.hip, tulip_loss_edge_*) is restated by the *32 functions:
+d32 = fl32(pred - target); e_h = ((d[+1,-1] - d[-1,-1]) + 2 (d[+1,0] - d[-1,0])) + (d[+1,+1] - d[-1,+1]), one rounding per
+operation (d[dy,dx]; e_v: the transposed pattern); ge = fl32(fl32(w) * g) with g the base gradient's fl32(gscale / n) (n_v with
+the mask); dpred = fl32(base_grad + fl32(ge * k)); edge32 = fl32(sum / n), the sum folded in double;
+total32 = fl32(base32 + fl32(fl32(w) * edge32)).  edge_weight=0.0 (the default): every function returns what it returns without
+the keyword, bit for bit.
 """
 from __future__ import annotations
 
@@ -170,11 +194,149 @@ def pixel_loss(pred, target, log_transform: bool, valid_min=None) -> np.float64:
         return np.mean(np.abs(pred - target))
 
 
-def torch_loss(kind: str, pred, target, valid_min=None):
+def check_edge_weight(w) -> float:
+    """The weight of TULIP(loss_edge_weight=...): a finite float >= 0, returned as a Python float (ValueError for a bool, an int,
+    a NaN, an infinity, a negative value or any other type: check_valid_min's strictness)."""
+    if isinstance(w, (bool, np.bool_)) or not isinstance(w, (float, np.floating)) or not np.isfinite(w) or w < 0:
+        raise ValueError(f"loss_edge_weight must be a finite float >= 0, got {w!r}")
+    return float(w)
+
+
+def _shifted(a: np.ndarray, dy: int, dx: int) -> np.ndarray:
+    """s[..., y, x] = a[..., y + dy, x + dx], 0 outside the plane (the last two axes); dy, dx in -1..1"""
+    H, W = a.shape[-2:]
+    p = np.zeros(a.shape[:-2] + (H + 2, W + 2), dtype=a.dtype)
+    p[..., 1:H + 1, 1:W + 1] = a
+    return p[..., 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+
+
+def _responses(d: np.ndarray):
+    """(e_h, e_v) of d (..., H, W) in d's dtype, in the device's order of operations"""
+    s = lambda dy, dx: _shifted(d, dy, dx)
+    with np.errstate(all="ignore"):
+        two = d.dtype.type(2)
+        e_h = ((s(1, -1) - s(-1, -1)) + two * (s(1, 0) - s(-1, 0))) + (s(1, 1) - s(-1, 1))
+        e_v = ((s(-1, 1) - s(-1, -1)) + two * (s(0, 1) - s(0, -1))) + (s(1, 1) - s(1, -1))
+    return e_h, e_v
+
+
+def _plane_check(a: np.ndarray) -> np.ndarray:
+    if a.ndim < 2:
+        raise ValueError(f"the edge term needs planes (..., H, W), got {a.shape}")
+    return a
+
+
+def edge_responses(d):
+    """(e_h, e_v): the two Sobel responses of d (..., H, W) in float64, every plane on its own, zero outside it -- what the
+    reference's HorizontalEdgeDetectionCNN / VerticalEdgeDetectionCNN return for d."""
+    return _responses(_plane_check(np.asarray(d, dtype=np.float64)))
+
+
+def edge_responses32(d):
+    """edge_responses in float32 with the device's roundings (d: float32 already, or rounded to it here)"""
+    return _responses(_plane_check(np.asarray(d, dtype=np.float32)))
+
+
+def _edge_diff(pred, target, valid_min, dtype):
+    """(d, mask): d = pred - target in dtype, +0 by selection at the invalid pixels"""
+    m = valid_mask(target, valid_min)
+    with np.errstate(all="ignore"):
+        d = np.asarray(pred, dtype=dtype) - np.asarray(target, dtype=dtype)
+    return _plane_check(np.where(m, d, dtype(0))), m
+
+
+def _adjoint(s_h: np.ndarray, s_v: np.ndarray) -> np.ndarray:
+    """k[p, q] = sum_{i,j} K_h[i,j] s_h[p-i+1, q-j+1] + K_v[i,j] s_v[p-i+1, q-j+1] (0 outside the plane)"""
+    h, v = (lambda dy, dx: _shifted(s_h, dy, dx)), (lambda dy, dx: _shifted(s_v, dy, dx))
+    k_h = (h(-1, 1) + 2 * h(-1, 0) + h(-1, -1)) - (h(1, 1) + 2 * h(1, 0) + h(1, -1))
+    k_v = (v(1, -1) + 2 * v(0, -1) + v(-1, -1)) - (v(1, 1) + 2 * v(0, 1) + v(-1, 1))
+    return k_h + k_v
+
+
+def _sign(e: np.ndarray) -> np.ndarray:
+    with np.errstate(all="ignore"):
+        return (e > 0).astype(np.int64) - (e < 0).astype(np.int64)           # a NaN: 0
+
+
+def _edge_k(d: np.ndarray, m: np.ndarray, responses) -> np.ndarray:
+    e_h, e_v = responses(d)
+    k = _adjoint(np.where(m, _sign(e_h), 0), np.where(m, _sign(e_v), 0))
+    return np.where(m, k, 0)
+
+
+def edge_value(pred, target, valid_min=None) -> np.float64:
+    """edge = (1/n) sum (|e_h| + |e_v|) of d = pred - target in float64; with valid_min over the responses centred on a valid
+    pixel, with n_v (0 when there is none)."""
+    d, m = _edge_diff(pred, target, valid_min, np.float64)
+    nv = int(m.sum())
+    if nv == 0:
+        return np.float64(0.0)
+    e_h, e_v = _responses(d)
+    with np.errstate(all="ignore"):
+        return np.sum((np.abs(e_h) + np.abs(e_v))[m]) / nv
+
+
+def edge_grad_int(pred, target, valid_min=None) -> np.ndarray:
+    """k = n * d(edge) / d(pred): an int64 array of pred's shape, every value in [-16, 16]; 0 at the invalid elements."""
+    d, m = _edge_diff(pred, target, valid_min, np.float64)
+    return _edge_k(d, m, _responses)
+
+
+def edge_grad32(pred, target, base_grad32, weight, gscale: float = 1.0, valid_min=None) -> np.ndarray:
+    """The device's dpred behind tulip_loss_edge_bwd, in float32: fl32(base_grad32 + fl32(ge * k)), ge = fl32(fl32(weight) * g),
+    g = fl32(gscale / n) (n_v with valid_min, 0 when there is none); +0 at the invalid elements."""
+    d, m = _edge_diff(pred, target, valid_min, np.float32)
+    k = _edge_k(d, m, _responses).astype(np.float32)
+    nv = int(m.sum())
+    with np.errstate(all="ignore"):
+        g = np.float32(gscale) / np.float32(nv) if nv else np.float32(0.0)
+        ge = np.float32(check_edge_weight(float(weight))) * g
+        out = np.asarray(base_grad32, dtype=np.float32) + ge * k
+    return np.where(m, out, np.float32(0.0)) if valid_min is not None else out
+
+
+def edge_total32(pred, target, base32, weight, valid_min=None):
+    """(edge32, total32) as the device forms them: edge32 = fl32(sum * (1 / n)) with the float32 terms fl32(|e_h| + |e_v|) summed
+    in double (the device sums a workgroup's terms in float32 first: the same bits wherever those sums are exact, integer
+    inputs for instance), total32 = fl32(base32 + fl32(fl32(weight) * edge32))."""
+    d, m = _edge_diff(pred, target, valid_min, np.float32)
+    nv = int(m.sum())
+    e_h, e_v = _responses(d)
+    with np.errstate(all="ignore"):
+        s = np.sum((np.abs(e_h) + np.abs(e_v))[m].astype(np.float64))
+        edge32 = np.float32(s * (1.0 / nv if nv else 0.0))
+        total32 = np.float32(base32) + np.float32(check_edge_weight(float(weight))) * edge32
+    return edge32, total32
+
+
+def _torch_edge(d):
+    """sum (|e_h| + |e_v|) of d (B, C, H, W) on torch tensors"""
+    import torch
+    import torch.nn.functional as F
+    k_h = torch.tensor([[-1.0, -2.0, -1.0], [0.0, 0.0, 0.0], [1.0, 2.0, 1.0]], dtype=d.dtype, device=d.device)
+    planes = d.reshape(-1, 1, *d.shape[-2:])
+    e_h = F.conv2d(planes, k_h[None, None], padding=1)
+    e_v = F.conv2d(planes, k_h.t()[None, None], padding=1)
+    return (e_h.abs() + e_v.abs()).reshape(d.shape)
+
+
+def torch_loss(kind: str, pred, target, valid_min=None, edge_weight=0.0):
     """The same definition on torch tensors, differentiable in pred (C detached, as the reference's .item() leaves it): what a
     test or a CPU experiment back-propagates through an autograd model.  With valid_min: over the valid elements (indexing, not
-    a product with the mask: a NaN at an invalid pixel reaches neither the value nor the gradient)."""
+    a product with the mask: a NaN at an invalid pixel reaches neither the value nor the gradient).  edge_weight > 0 adds the
+    edge term (pred, target: (B, C, H, W)); 0.0 returns the value without it, bit for bit."""
     import torch
+    edge_weight = check_edge_weight(edge_weight)
+    if edge_weight != 0.0:
+        base = torch_loss(kind, pred, target, valid_min)
+        d = pred - target
+        if check_valid_min(valid_min) is None:
+            return base + edge_weight * (_torch_edge(d).sum() / d.numel())
+        m = (target[:, :1] > valid_min).expand_as(target)
+        nv = int(m.sum())
+        if nv == 0:
+            return base
+        return base + edge_weight * (_torch_edge(torch.where(m, d, torch.zeros_like(d)))[m].sum() / nv)
     kind = check_loss(kind)
     d = pred - target
     if check_valid_min(valid_min) is not None:

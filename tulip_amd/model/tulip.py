@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..loss import check_loss, check_valid_min
+from ..loss import check_edge_weight, check_loss, check_valid_min
 
 __all__ = ["TULIP", "tulip_base", "tulip_large"]
 
@@ -173,7 +173,7 @@ class BasicBlockUp(_ParamHolder):  # tulip.py:441-475
 
 
 class TULIP(nn.Module):
-    """tulip.py:530-737.  Constructor signature and defaults are the reference's, followed by two keywords of this project's:
+    """tulip.py:530-737.  Constructor signature and defaults are the reference's, followed by three keywords of this project's:
 
     loss: "l1" (default: the reference's forward_loss, tulip.py:690-700), "l2" or "berhu" -- the training loss `forward` returns
     as total_loss and `loss.backward()` / Trainer differentiate (tulip_amd/loss.py is the definition; ValueError for another
@@ -188,7 +188,14 @@ class TULIP(nn.Module):
     the means over the n_v = in_chans * (valid pixels) valid elements, berHu's C the maximum over them, the gradient +0 at the
     others; no valid pixel gives zeros.  A NaN or an infinity in the prediction or the target at an invalid pixel changes
     nothing.  n_v is per call, as C is.  Fixed at construction; state_dict() does not carry it (ValueError for a bool, a NaN, an
-    infinity or another type)."""
+    infinity or another type).
+
+    loss_edge_weight: 0.0 (default: no edge term -- no buffer, no launch, every result as without the keyword) or a finite float
+    w > 0: total_loss = the loss above + w * mean(|e_h| + |e_v|), e_h / e_v the 3x3 Sobel responses of pred - target (the
+    reference's util/filter.py modules, which tulip.py:9 imports and never calls) per (b, c) plane with zero padding; with
+    loss_valid_min over the responses centred on a valid pixel, the difference taken as 0 at an invalid one (tulip_amd/loss.py is
+    the definition).  pixel_loss does not change.  Fixed at construction; state_dict() does not carry it (ValueError for a bool,
+    an int, a NaN, an infinity or a negative value)."""
 
     def __init__(self, img_size=(32, 2048), target_img_size=(128, 2048), patch_size=(4, 4), in_chans: int = 1,
                  embed_dim: int = 96, window_size=4, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
@@ -196,10 +203,11 @@ class TULIP(nn.Module):
                  drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True,
                  pixel_shuffle: bool = False, circular_padding: bool = False, swin_v2: bool = False,
                  log_transform: bool = False, patch_unmerging: bool = False, loss: str = "l1",
-                 loss_valid_min=None):
+                 loss_valid_min=None, loss_edge_weight: float = 0.0):
         super().__init__()
         self._loss = check_loss(loss)
         self._loss_valid_min = check_valid_min(loss_valid_min)
+        self._loss_edge_weight = check_edge_weight(loss_edge_weight)
         self.window_size = window_size
         self.depths, self.num_heads = tuple(depths), tuple(num_heads)
         self.num_layers = len(depths)
@@ -271,6 +279,11 @@ class TULIP(nn.Module):
     def loss_valid_min(self):
         """the valid-pixel threshold of the loss chosen at construction: None (no mask) or a float (tulip_amd/loss.py)"""
         return self._loss_valid_min
+
+    @property
+    def loss_edge_weight(self) -> float:
+        """the weight of the edge term chosen at construction: 0.0 (no term) or a positive float (tulip_amd/loss.py)"""
+        return self._loss_edge_weight
 
     # ------------------------------------------------------------------ engine plumbing
     def engine(self):

@@ -424,6 +424,47 @@ def loss_value_m(pred, target, stats, value_partials, n, chans, chan_stride, val
                                          float(valid_min), _p(counts), _stream()), "tulip_loss_value_m")
 
 
+def loss_edge_blocks(planes, H, W):
+    """workgroups of the tulip_loss_edge_* launches over `planes` planes of H x W: the entries of `edge_partials` in use"""
+    return _lib.load().tulip_loss_edge_blocks(int(planes), int(H), int(W))
+
+
+def loss_edge_stats(pred, target, edge_partials, planes, H, W, mask=None, counts=None):
+    """edge_partials[wg] = the workgroup's sum of |e_h| + |e_v| of d = pred - target (tulip_amd/loss.py, the edge term); mask:
+    (chans, valid_min) -- the responses centred on a valid pixel only (`counts` is not read by this launch)."""
+    lib = _lib.load()
+    if mask is None:
+        check(lib.tulip_loss_edge_stats(_p(pred), _p(target), _p(edge_partials), int(planes), int(H), int(W), _stream()),
+              "tulip_loss_edge_stats")
+    else:
+        check(lib.tulip_loss_edge_stats_m(_p(pred), _p(target), _p(edge_partials), int(planes), int(H), int(W), int(mask[0]),
+                                          float(mask[1]), _stream()), "tulip_loss_edge_stats_m")
+
+
+def loss_edge_bwd(pred, target, gscale_dev, gscale, weight, dpred, planes, H, W, mask=None, counts=None):
+    """dpred += weight * gscale * d(edge) / d(pred) in place, behind the base gradient; mask: (chans, valid_min) with `counts` --
+    n_v in place of n, +0 at the invalid elements."""
+    lib = _lib.load()
+    if mask is None:
+        check(lib.tulip_loss_edge_bwd(_p(pred), _p(target), _p(gscale_dev), float(gscale), float(weight), _p(dpred), int(planes),
+                                      int(H), int(W), _stream()), "tulip_loss_edge_bwd")
+    else:
+        check(lib.tulip_loss_edge_bwd_m(_p(pred), _p(target), _p(gscale_dev), float(gscale), float(weight), _p(dpred), int(planes),
+                                        int(H), int(W), int(mask[0]), float(mask[1]), _p(counts), _stream()), "tulip_loss_edge_bwd_m")
+
+
+def loss_edge_final(edge_partials, edge_out, losses, weight, planes, H, W, mask=None, counts=None):
+    """edge_out[0] = the edge term, losses[0] += weight * edge_out[0], behind the base loss's final launch; mask: 1 / n_v from
+    `counts`."""
+    lib = _lib.load()
+    if mask is None:
+        check(lib.tulip_loss_edge_final(_p(edge_partials), _p(edge_out), _p(losses), float(weight), int(planes), int(H), int(W),
+                                        _stream()), "tulip_loss_edge_final")
+    else:
+        check(lib.tulip_loss_edge_final_m(_p(edge_partials), _p(edge_out), _p(losses), float(weight), int(planes), int(H), int(W),
+                                          _p(counts), _stream()), "tulip_loss_edge_final_m")
+
+
 def loss_final_m(kind, stats, value_partials, losses, n, log_transform, counts, n_valid):
     """loss_final with 1 / n_v formed on the device from counts (both losses 0 when n_v == 0); n_valid receives n_v."""
     check(_lib.load().tulip_loss_final_m(_loss_kind(kind), _p(stats), _p(value_partials), _p(losses), n, int(log_transform),

@@ -36,7 +36,7 @@ from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
 from .guard import check_skip_nonfinite
-from .loss import check_loss, check_valid_min
+from .loss import check_edge_weight, check_loss, check_valid_min
 from .engine import ALIGN
 
 
@@ -122,7 +122,11 @@ class Trainer:
         The valid-pixel mask is the model's too (TULIP(loss_valid_min=...)): the loss, `losses[1]` and berHu's C are then over the
         pixels whose target range exceeds the threshold, n_v of them counted on the device per micro-batch and per rank;
         `loss_valid` is the device int64 of the last backward.  A NaN in a target pixel that the mask drops costs no step under
-        skip_nonfinite.  exchange="sharded" with a mask raises ValueError; state_dict() does not carry the setting."""
+        skip_nonfinite.  exchange="sharded" with a mask raises ValueError; state_dict() does not carry the setting.
+        The edge term is the model's as well (TULIP(loss_edge_weight=w)): with w > 0 `losses[0]` is the total, the loss above plus
+        w times the mean Sobel response of pred - target, formed on the device inside the captured graphs per micro-batch and
+        per rank; `edge_loss` is the device float of the last forward's term (AttributeError at w == 0).  exchange="sharded" with
+        w > 0 raises ValueError; state_dict() records w as "loss_edge_weight"."""
         skip_nonfinite = check_skip_nonfinite(skip_nonfinite)
         self.loss = check_loss(getattr(model, "loss", "l1"))
         self.loss_valid_min = check_valid_min(getattr(model, "loss_valid_min", None))
@@ -130,6 +134,9 @@ class Trainer:
             raise ValueError("exchange='sharded' with a loss other than 'l1' is not supported: use exchange='allreduce'")
         if self.loss_valid_min is not None and exchange == "sharded":
             raise ValueError("exchange='sharded' with loss_valid_min is not supported: use exchange='allreduce'")
+        self.loss_edge_weight = check_edge_weight(getattr(model, "loss_edge_weight", 0.0))
+        if self.loss_edge_weight != 0.0 and exchange == "sharded":
+            raise ValueError("exchange='sharded' with loss_edge_weight is not supported: use exchange='allreduce'")
         if skip_nonfinite and exchange == "sharded":
             raise ValueError("exchange='sharded' with skip_nonfinite is not supported (the per-bucket optimizer steps before the "
                              "global norm exists): use exchange='allreduce'")
@@ -364,6 +371,14 @@ class Trainer:
             raise AttributeError("this Trainer's model has no valid-pixel mask: build the model with loss_valid_min=...")
         return self.P.loss_valid
 
+    @property
+    def edge_loss(self) -> torch.Tensor:
+        """The edge term mean(|e_h| + |e_v|) of the last forward, before its weight: a device float (no sync); models built with
+        loss_edge_weight > 0 only."""
+        if self.loss_edge_weight == 0.0:
+            raise AttributeError("this Trainer's model has no edge term: build the model with loss_edge_weight > 0")
+        return self.P.loss_edge
+
     def _guard_word(self, k: int) -> int:
         if self._guard_state is None:
             raise AttributeError("this Trainer has no non-finite guard: build it with skip_nonfinite=True")
@@ -563,7 +578,7 @@ class Trainer:
         if self.skip_nonfinite:                    # the optimizer's step count is the APPLIED count, which only the device knows
             applied, skipped, consecutive = (int(x) for x in self._guard_state.tolist())
         sd = {"step": applied, "micro": self.micro, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
-              "weight_decay": self.wd, "accum_iter": self.accum_iter, "lr_scales": dict(self.lr_scales),
+              "weight_decay": self.wd, "accum_iter": self.accum_iter, "loss_edge_weight": self.loss_edge_weight, "lr_scales": dict(self.lr_scales),
               "exp_avg": {n: cut(self.m, n) for n in W.names}, "exp_avg_sq": {n: cut(self.v, n) for n in W.names},
               "grad": {n: cut(self.g, n) for n in W.names} if self.micro % self.accum_iter else None,
               "drop_seed": int(self.eng._drop_seed), "drop_counter": int(self.eng._drop_counter.item()),
@@ -577,6 +592,17 @@ class Trainer:
         if self.skip_nonfinite:                    # (likewise)
             sd["guard"] = {"applied": applied, "skipped": skipped, "consecutive": consecutive}
         return sd
+
+    def _report_saved_edge_weight(self, sd: dict) -> bool:
+        """The edge term is the model's setting, fixed at its construction: a state saved under another weight (a dictionary without
+        the key: 0.0) is loaded all the same, and the difference is reported on stderr -- the run continues with another loss than it
+        was saved with.  True when they differ."""
+        saved = float(sd.get("loss_edge_weight", 0.0))
+        if saved == self.loss_edge_weight:
+            return False
+        sys.stderr.write(f"tulip_amd.Trainer: the optimizer state was saved with loss_edge_weight={saved!r} and this Trainer's model "
+                         f"was built with {self.loss_edge_weight!r}: the model's value stays\n")
+        return True
 
     def load_state_dict(self, sd: dict) -> None:
         W = self.eng.params
@@ -600,6 +626,7 @@ class Trainer:
         elif self._clip_grad is None and sd.get("clip_grad") is not None:
             sys.stderr.write("tulip_amd.Trainer: the optimizer state was saved with gradient clipping ('clip_grad') and this Trainer "
                              "clips nothing (clip_grad=None): ignored\n")
+        self._report_saved_edge_weight(sd)
         put = lambda flat, n, t: flat[W.offset[n]:W.offset[n] + W.numel[n]].copy_(t.reshape(-1).to(flat.dtype))
         for n in W.names:
             put(self.m, n, sd["exp_avg"][n])

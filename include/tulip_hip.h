@@ -742,6 +742,36 @@ int tulip_range_prep_aug(const void* raw, int raw_dtype, int64_t batch_stride, i
                          int log_transform, const int64_t* sample_ids, uint64_t seed, int flags, uint32_t beam_threshold,
                          uint32_t point_threshold, int32_t* params_out, hipStream_t stream);
 
+/* Multi-channel batches: the two calls above with trailing (C, chan_stride, chan_scale, chan_log), for raw images of C in 1..4
+ * channels ([range, intensity, ...]; float32 only).  Channel c of pixel (i,j) of image b is raw[b*batch_stride + base_offset +
+ * i*row_stride + j*col_stride + c*chan_stride]; hi (B,C,H,W) and/or lo (B,C,H/row_factor,W/col_factor), planes.  chan_scale:
+ * HOST pointer to C-1 floats, the scale s_c of channels 1..C-1 (read during the call, passed to the kernel by value; may be NULL
+ * at C == 1); chan_log bit c-1: log1p on channel c.  Host definition: tulip_amd/prep_channels.py.
+ *   channel 0:  v0 = the value of tulip_range_prep (raw0*scale -> gate -> log1p if log_transform), and nothing else: bit for bit
+ *               the single-channel output.
+ *   hole:       the pixel is a hole iff raw0*scale after the gate, BEFORE the log, == 0.0f (true for -0.0, false for a NaN).
+ *   channel c:  u = raw_c * s_c (one float32 multiply);  u = hole ? +0.0f : u  (a select: a NaN, infinite or negative raw_c in a
+ *               hole gives +0.0f);  u = log1pf(u) if bit c-1 of chan_log.
+ * Subsampling, phases and roll_shift (tulip_range_prep_c), and the rotation, mirror, start row and beam / point drops
+ * (tulip_range_prep_aug_c; the draws do not depend on C) apply to every channel alike: output channel c of the augmented call is
+ * bit for bit the gather of tulip_range_prep_aug's comment applied to plain channel c, a dropped low-res pixel is +0.0f in all C
+ * channels, the target is never dropped.  The interleaved row-major payload (chan_stride 1, col_stride 2 or 4 >= C, the
+ * alignment of the single-channel 16-byte kernels) is read once with 16-byte loads, a thread owning 4 output pixels of all C
+ * planes; anything else goes through the LDS-tile form.  One launch each, nothing allocated, no host state, graph-capturable.
+ * TULIP_ERR_ARG before any launch: whatever the call above refuses, raw_dtype != 0, C < 1, C > 4, chan_scale NULL at C > 1,
+ * chan_log bits at or above C-1. */
+int tulip_range_prep_c(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride, int64_t col_stride,
+                       int64_t base_offset, float* hi, float* lo, int B, int H, int W, int row_factor, int col_factor,
+                       int row_phase, int col_phase, float scale, int gate, float min_range, float max_range,
+                       int log_transform, int roll_shift, hipStream_t stream, int C, int64_t chan_stride,
+                       const float* chan_scale, uint32_t chan_log);
+int tulip_range_prep_aug_c(const void* raw, int raw_dtype, int64_t batch_stride, int64_t row_stride, int64_t col_stride,
+                           int64_t base_offset, float* hi, float* lo, int B, int H, int W, int row_factor, int col_factor,
+                           int row_phase, int col_phase, float scale, int gate, float min_range, float max_range,
+                           int log_transform, const int64_t* sample_ids, uint64_t seed, int flags, uint32_t beam_threshold,
+                           uint32_t point_threshold, int32_t* params_out, hipStream_t stream, int C, int64_t chan_stride,
+                           const float* chan_scale, uint32_t chan_log);
+
 /* ---- evaluation post-processing and 3-D metrics (engine_upsampling.py:126-355,361-608; util/evaluation.py) ---- */
 
 /* MC-dropout aggregate (engine_upsampling.py:421-426): preds (passes, n) -> out (n):

@@ -3,6 +3,8 @@
   prep     : tulip_range_prep, KITTI B=8 from the interleaved .npy payload -> GB/s against the HBM roofline
   prep_aug : tulip_range_prep_aug on the same two workloads (roll + flip + row phase, beam_drop 0.1, point_drop 0.05), timed in
              alternation with the plain launch: per-pair ratio and its spread over the repeats; `--only prep` runs just these
+  prep_ch2 : RangePrep(in_chans=2) (tulip_range_prep_c, one launch) on the same two workloads from the interleaved payload, in
+             alternation with the single-channel entry point once per channel plus the hole select in torch
   infer    : eval forward, tulip_base KITTI B=8, HIP-graph replay -> images/s (the MCdrop tile)
   evaluate : per-image post-processing + projection + voxel metrics + Chamfer -> ms/image, Chamfer pair rate
              against the fp32 vector-ALU rate, and the oracle (numpy/torch CPU) timed on the same image
@@ -100,6 +102,41 @@ def main():
         pk = D.RangePrep("durlar", (32, 2048), (128, 2048), True, augment=RangeAugment(seed=0, **kw))
         a, b = paired(lambda: prep_big(big), lambda: pk(big, sample_ids=ids64), 50, 5)
         out[f"prep_large_aug_{name}_only"] = pair_record(f"durlar B=64 128x2048, {kw}", a, b, algo_big)
+    # ---- two-channel batches: one launch of RangePrep(in_chans=2) against what a caller had before it -- the single-channel entry
+    # point once per channel (its own base offset and scale) and the hole select in torch -- in alternation
+    from tulip_amd import ops
+
+    def ch2_record(name, ds, lo_size, hi_size, pay, iters):
+        Bc, Hc, Wc, f = pay.shape[0], hi_size[0], hi_size[1], hi_size[0] // lo_size[0]
+        one = D.RangePrep(ds, lo_size, hi_size, True)
+        two = D.RangePrep(ds, lo_size, hi_size, True, in_chans=2)
+
+        def alternative():
+            lo0, hi0 = one(pay)
+            hi1 = torch.empty_like(hi0)
+            lo1 = torch.empty_like(lo0)
+            ops.range_prep(pay, 0, Hc * Wc * 2, Wc * 2, 2, 1, hi1, lo1, Bc, Hc, Wc, f, 1, 0, 0, 1.0, False, 0.0, 0.0, False, 0)
+            hi1.masked_fill_(hi0 == 0, 0.0)
+            lo1.masked_fill_(lo0 == 0, 0.0)
+            return lo0, lo1, hi0, hi1
+        lo, hi = two(pay)
+        lo0, lo1, hi0, hi1 = alternative()
+        assert torch.equal(hi[:, 0:1], hi0) and torch.equal(lo[:, 0:1], lo0) and torch.equal(hi[:, 1:2], hi1) and \
+            torch.equal(lo[:, 1:2], lo1)
+        a, b = paired(alternative, lambda: two(pay), iters, 7)
+        ratio = sorted(y / x for x, y in zip(a, b))
+        med = lambda v: sorted(v)[len(v) // 2]
+        algo2 = Bc * Hc * Wc * (4 * 2 + 2 * (4 + 4 / f))            # 4*Cr bytes per pixel in, C*(4 + 4/f) out
+        out[name] = {"workload": f"{ds} B={Bc} {Hc}x{Wc} from (H,W,2) payload, in_chans=2",
+                     "alternative": "tulip_range_prep per channel (2 launches) + masked_fill_ per output (4 torch launches); "
+                                    "its two channels stay separate (B,1,..) tensors: no concatenation is timed",
+                     "alt_ms": med(a), "alt_ms_min_max": [min(a), max(a)], "ms": med(b), "ms_min_max": [min(b), max(b)],
+                     "algorithmic_GBps": algo2 / med(b) / 1e6, "ratio_one_launch_over_alt": med(ratio),
+                     "ratio_min_max": [ratio[0], ratio[-1]], "pairs": len(a)}
+    ch2_record("prep_ch2", "kitti", (16, 1024), (64, 1024), payload, 200)
+    big2 = torch.stack([big, torch.rand_like(big)], -1).contiguous()
+    ch2_record("prep_large_ch2", "durlar", (32, 2048), (128, 2048), big2, 50)
+    del big2
     if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "prep":
         print(json.dumps(out, indent=1))
         return

@@ -223,6 +223,10 @@ SIGNATURES = {
     # ... with the per-sample augmentation: roll_shift -> sample_ids, seed, flags (AUG_* below), the two drop thresholds, params_out
     "tulip_range_prep_aug": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, P, ctypes.c_uint64, I, ctypes.c_uint32,
                              ctypes.c_uint32, P, P],
+    # ... multi-channel batches: both with trailing (C, chan_stride, chan_scale: HOST float[C-1], chan_log bit mask)
+    "tulip_range_prep_c": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, I, P, I, L, P, ctypes.c_uint32],
+    "tulip_range_prep_aug_c": [P, I, L, L, L, L, P, P, I, I, I, I, I, I, I, F, I, F, F, I, P, ctypes.c_uint64, I, ctypes.c_uint32,
+                               ctypes.c_uint32, P, P, I, L, P, ctypes.c_uint32],
     "tulip_mc_aggregate": [P, I, L, F, P, P],
     "tulip_eval_postprocess": [P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "tulip_range_to_xyz": [P, P, P, P, P, F, I, I, P, P],

@@ -9,10 +9,14 @@ collates.  Here the host only reads file payloads into one pinned staging buffer
 + flipped float16 .rimg) and writes the model's (low_res, high_res) batch.  No CPU fallback: without the
 HIP library `RangePrep.__call__` raises.  `RangePrep(augment=RangeAugment(...))` makes that launch draw a
 rotation, a mirror, the start row and beam / point drops per sample from (seed, sample id)
-(tulip_range_prep_aug; tulip_amd/augment.py is the definition).
+(tulip_range_prep_aug; tulip_amd/augment.py is the definition).  `RangePrep(in_chans=C)` builds C-channel batches from the
+[range, intensity, ...] pixels of the payload in the same one launch (tulip_range_prep_c / tulip_range_prep_aug_c;
+tulip_amd/prep_channels.py is the definition).
 """
 from __future__ import annotations
 
+import math
+import numbers
 import os
 import struct
 from typing import Iterator, List, Optional, Sequence, Tuple
@@ -39,7 +43,8 @@ class RangePrep:
 
     def __init__(self, dataset_select: str, img_size_low_res: Sequence[int], img_size_high_res: Sequence[int],
                  log_transform: bool = False, roll_shift: Optional[int] = None, row_phase: int = 0,
-                 col_phase: int = 0, augment: Optional[RangeAugment] = None):
+                 col_phase: int = 0, augment: Optional[RangeAugment] = None, in_chans: int = 1,
+                 channel_scale: Optional[Sequence[float]] = None, channel_log: Optional[Sequence[bool]] = None):
         if dataset_select not in DATASET_PREP:
             raise KeyError(dataset_select)          # generate_dataset: dataset_list[args.dataset_select] (datasets.py:49-51)
         self.scale, self.gate = DATASET_PREP[dataset_select]
@@ -62,16 +67,35 @@ class RangePrep:
             if augment.row_phase and row_phase != 0:
                 raise ValueError("augment.row_phase draws the start row per sample: it cannot be combined with row_phase != 0")
         self.augment = augment
+        # multi-channel batches ([range, intensity, ...] pixels -> (B,C,..) planes): tulip_amd/prep_channels.py.  1: the launches of before
+        if isinstance(in_chans, (bool, np.bool_)) or not isinstance(in_chans, numbers.Integral) or not 1 <= in_chans <= 4:
+            raise ValueError(f"in_chans must be an int in 1..4, got {in_chans!r}")
+        self.in_chans = C = int(in_chans)
+        scales = [1.0] * (C - 1) if channel_scale is None else list(channel_scale)
+        logs = [False] * (C - 1) if channel_log is None else list(channel_log)
+        if len(scales) != C - 1 or len(logs) != C - 1:
+            raise ValueError(f"in_chans={C} takes {C - 1} channel_scale and channel_log entries (channels 1..{C - 1}), got "
+                             f"{len(scales)} and {len(logs)}")
+        for v in scales:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+                raise ValueError(f"channel_scale must hold finite real numbers, got {v!r}")
+        for v in logs:
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"channel_log must hold bools, got {v!r}")
+        self.channel_scale = tuple(float(v) for v in scales)
+        self.channel_log = tuple(bool(v) for v in logs)
 
     # -- raw layouts ---------------------------------------------------------------------------------
     def _run(self, raw: torch.Tensor, dtype_code: int, sb: int, si: int, sj: int, base: int, B: int,
-             want_hi: bool, want_lo: bool, sample_ids=None, params_out=None):
+             want_hi: bool, want_lo: bool, sample_ids=None, params_out=None, sc: int = 1):
         ids = self._check_ids(sample_ids, B)        # ValueError before the device is touched
         if not raw.is_cuda:
             raise RuntimeError("tulip_amd.data.RangePrep runs on the GPU only (HIP kernel, no CPU fallback)")
         dev = raw.device
-        hi = torch.empty(B, 1, self.H, self.W, dtype=torch.float32, device=dev) if want_hi else None
-        lo = torch.empty(B, 1, self.h, self.w, dtype=torch.float32, device=dev) if want_lo else None
+        C = self.in_chans
+        hi = torch.empty(B, C, self.H, self.W, dtype=torch.float32, device=dev) if want_hi else None
+        lo = torch.empty(B, C, self.h, self.w, dtype=torch.float32, device=dev) if want_lo else None
+        chan = (C, sc, self.channel_scale, self.channel_log)
         gmin, gmax = self.gate if self.gate is not None else (0.0, 0.0)
         if self.augment is not None:
             aug = self.augment
@@ -82,9 +106,19 @@ class RangePrep:
             if params_out is not None and (params_out.dtype != torch.int32 or tuple(params_out.shape) != (B, 4) or
                                            not params_out.is_contiguous() or params_out.device != dev):
                 raise ValueError("params_out must be a contiguous (B,4) int32 tensor on the device of raw")
+            if C > 1:
+                ops.range_prep_aug_c(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
+                                     self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform, ids,
+                                     aug.seed, aug.flags, *aug.thresholds, params_out, *chan)
+                return lo, hi
             ops.range_prep_aug(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
                                self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform, ids,
                                aug.seed, aug.flags, *aug.thresholds, params_out)
+            return lo, hi
+        if C > 1:
+            ops.range_prep_c(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
+                             self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform,
+                             self.roll_shift, *chan)
             return lo, hi
         ops.range_prep(raw, dtype_code, sb, si, sj, base, hi, lo, B, self.H, self.W, self.f, self.fw, self.row_phase,
                        self.col_phase, self.scale, self.gate is not None, gmin, gmax, self.log_transform,
@@ -112,7 +146,8 @@ class RangePrep:
     def __call__(self, raw: torch.Tensor, want_hi: bool = True, want_lo: bool = True, sample_ids=None, params_out=None):
         """raw: (B,H,W) float32 metres, or the (B,H,W,2) [range, intensity] payload of B .npy files
         (channel 0 is read in place).  Returns (low_res (B,1,h,w), high_res (B,1,H,W)).  With augment: sample_ids (B ids) and
-        optionally params_out, a (B,4) int32 device tensor that receives (s, flip, p, 0) per sample."""
+        optionally params_out, a (B,4) int32 device tensor that receives (s, flip, p, 0) per sample.  With in_chans = C > 1: raw
+        is the (B,H,W,Cr >= C) payload, its first C channels become (B,C,h,w) and (B,C,H,W) (tulip_amd/prep_channels.py)."""
         if raw.dtype != torch.float32 or not raw.is_contiguous():
             raise TypeError("raw must be a contiguous float32 tensor")
         if raw.dim() == 4:
@@ -123,6 +158,9 @@ class RangePrep:
             sj = 1
         else:
             raise ValueError("raw must be (B,H,W) or (B,H,W,C)")
+        if self.in_chans > 1 and (raw.dim() != 4 or C < self.in_chans):
+            raise ValueError(f"in_chans={self.in_chans} needs a (B,H,W,Cr) payload with Cr >= {self.in_chans}, got "
+                             f"{tuple(raw.shape)}")
         if (H, W) != (self.H, self.W):
             raise ValueError(f"raw image is {H}x{W}, img_size_high_res is {self.H}x{self.W}")
         return self._run(raw, 0, H * W * sj, W * sj, sj, 0, B, want_hi, want_lo, sample_ids, params_out)
@@ -132,6 +170,8 @@ class RangePrep:
         """payload: (B, s1, s0) float16, the bytes of B .rimg files after their (s0, s1) header.  The
         reference reshapes to (s1, s0), transposes and flips both axes (datasets.py:181-193): pixel (i,j)
         is payload[s1-1-j, s0-1-i], read in place through negative strides."""
+        if self.in_chans > 1:
+            raise ValueError(f"a .rimg payload holds one channel: from_rimg cannot feed in_chans={self.in_chans}")
         if payload.dtype != torch.float16 or payload.dim() != 3 or not payload.is_contiguous():
             raise TypeError("payload must be a contiguous (B, s1, s0) float16 tensor")
         B, s1, s0 = payload.shape
@@ -220,6 +260,8 @@ class DeviceRangeLoader:
         for chunk, ids in self.batches():
             paths = [self.files[i] for i in chunk]
             rimg = paths[0].lower().endswith(".rimg")
+            if rimg and getattr(self.prep, "in_chans", 1) > 1:
+                raise ValueError(f"{paths[0]}: a .rimg file holds one channel, the RangePrep has in_chans={self.prep.in_chans}")
             pays = [read_rimg_payload(p)[2] for p in paths] if rimg else [read_npy_payload(p) for p in paths]
             dev = self._upload(pays, torch.float16 if rimg else torch.float32, ids if aug else None)
             kw = {}

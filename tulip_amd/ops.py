@@ -535,6 +535,38 @@ def range_prep_aug(raw, raw_dtype, batch_stride, row_stride, col_stride, base_of
                                            int(point_threshold), _p(params_out), _stream()), "tulip_range_prep_aug")
 
 
+def _chan_args(C, chan_stride, chan_scale, chan_log):
+    """the trailing (C, chan_stride, chan_scale, chan_log) of the multi-channel calls: the C-1 scales as a host float array (the
+    entry point copies them into the kernel arguments before it returns), the C-1 log flags as a bit mask"""
+    scales = (ctypes.c_float * max(1, C - 1))(*[float(s) for s in chan_scale])
+    mask = sum(1 << k for k, on in enumerate(chan_log) if on)
+    return int(C), int(chan_stride), scales, mask
+
+
+def range_prep_c(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor,
+                 col_factor, row_phase, col_phase, scale, gate, min_range, max_range, log_transform, roll_shift, C, chan_stride,
+                 chan_scale, chan_log):
+    """tulip_range_prep_c: range_prep for C-channel pixels into (B,C,..) planes; chan_scale / chan_log: the C-1 scales and log
+    flags of channels 1..C-1 (tulip_amd/prep_channels.py is the host definition)."""
+    check(_lib.load().tulip_range_prep_c(_p(raw), raw_dtype, batch_stride, row_stride, col_stride, base_offset, _p(hi),
+                                         _p(lo), B, H, W, row_factor, col_factor, row_phase, col_phase, float(scale),
+                                         int(gate), float(min_range), float(max_range), int(log_transform),
+                                         int(roll_shift), _stream(), *_chan_args(C, chan_stride, chan_scale, chan_log)),
+          "tulip_range_prep_c")
+
+
+def range_prep_aug_c(raw, raw_dtype, batch_stride, row_stride, col_stride, base_offset, hi, lo, B, H, W, row_factor,
+                     col_factor, row_phase, col_phase, scale, gate, min_range, max_range, log_transform, sample_ids, seed,
+                     flags, beam_threshold, point_threshold, params_out, C, chan_stride, chan_scale, chan_log):
+    """tulip_range_prep_aug_c: range_prep_aug for C-channel pixels; every channel shares the sample's draws."""
+    check(_lib.load().tulip_range_prep_aug_c(_p(raw), raw_dtype, batch_stride, row_stride, col_stride, base_offset, _p(hi),
+                                             _p(lo), B, H, W, row_factor, col_factor, row_phase, col_phase, float(scale),
+                                             int(gate), float(min_range), float(max_range), int(log_transform),
+                                             _p(sample_ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), int(beam_threshold),
+                                             int(point_threshold), _p(params_out), _stream(),
+                                             *_chan_args(C, chan_stride, chan_scale, chan_log)), "tulip_range_prep_aug_c")
+
+
 # ---- evaluation post-processing / metrics (csrc/evalpost.hip)
 def mc_aggregate(preds, passes, n, noise_threshold, out):
     check(_lib.load().tulip_mc_aggregate(_p(preds), passes, n, float(noise_threshold), _p(out), _stream()),

@@ -789,6 +789,31 @@ int tulip_eval_postprocess(const float* pred, const float* hi, const float* lo, 
                            double* partials, float* mae_out, int H, int W, int h, int w, int log_transform,
                            float gate_min, float gate_max, float keep_close, hipStream_t stream);
 
+/* ---- the two above for images of C = 2..4 channels ([range, intensity, ...] planes; the reference evaluates one channel only, so
+ * the definition is this project's: tulip_amd/eval_channels.py is its host form) ----
+ *
+ * tulip_eval_postprocess_c: pred/hi (C,H,W), lo (C,h,w), pred_img/hi_img (C,H,W).  Channel 0 is tulip_eval_postprocess on the
+ * channel-0 planes, expression for expression (its planes are bit-identical).  A pixel is a prediction hole iff channel 0 is
+ * == 0.0f after the gate, before the rows are restored (true for -0.0f; a NaN fails the gate); a valid target pixel iff the
+ * target's channel 0 is > 0 after the expm1 (false for a NaN).  Channel c >= 1: expm1 of pred, hi and lo when bit c-1 of
+ * chan_log_bits is set (RangePrep(channel_log=...)); pred = hole ? +0.0f : pred (a select); sum|pred-hi| before the restore;
+ * when w==W rows 0::H/h give sum|pred-lo| and are replaced by lo; keep_close>0: where the final channel 0 of an image exceeds
+ * it, all C channels of that image's pixel become 0.  metrics (3*C+1 floats) = {mae[C], mae_low_res[C], mae_valid[C], n_valid}:
+ * float64 sums, float32(sum * inv); mae_valid[c] = sum over the valid target pixels / n_valid (0 when there is none), taken
+ * before the restore.  partials: scratch of (3*C+1)*1024 doubles.  One grid-stride launch and a single-block fold.
+ *
+ * tulip_mc_aggregate_c: preds (passes, C, n) -> out (C, n): per channel the float64 mean rounded to float32; the drop decision
+ * is channel 0's (sd0 > noise_threshold*mean0, unbiased std) and zeroes the pixel in all C channels; out[0:n] is bit for bit
+ * tulip_mc_aggregate of preds[:, 0].
+ *
+ * TULIP_ERR_ARG before any launch: what the single-channel calls refuse, C outside 2..4, w <= 0, chan_log_bits at or above bit
+ * C-1. */
+int tulip_mc_aggregate_c(const float* preds, int passes, int C, int64_t n, float noise_threshold, float* out,
+                         hipStream_t stream);
+int tulip_eval_postprocess_c(const float* pred, const float* hi, const float* lo, float* pred_img, float* hi_img,
+                             double* partials, float* metrics, int H, int W, int h, int w, int C, int log_transform,
+                             uint32_t chan_log_bits, float gate_min, float gate_max, float keep_close, hipStream_t stream);
+
 /* Range image -> (H*W,3) float32 points, row-major pixel order (evaluation.py img_to_pcd_kitti :52-87 and
  * img_to_pcd_carla :90-116): r = img*max_range; x = (sin_h[j]*cos_v[i])*r; y = (cos_h[j]*cos_v[i])*r;
  * z = sin_v[i]*r, float32 products in that order (bit exact against numpy given the same tables). */

@@ -229,6 +229,9 @@ SIGNATURES = {
                                ctypes.c_uint32, P, P, I, L, P, ctypes.c_uint32],
     "tulip_mc_aggregate": [P, I, L, F, P, P],
     "tulip_eval_postprocess": [P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
+    # ... for C = 2..4 channel images (tulip_amd/eval_channels.py): + C (, chan_log bit mask)
+    "tulip_mc_aggregate_c": [P, I, I, L, F, P, P],
+    "tulip_eval_postprocess_c": [P, P, P, P, P, P, P, I, I, I, I, I, I, ctypes.c_uint32, F, F, F, P],
     "tulip_range_to_xyz": [P, P, P, P, P, F, I, I, P, P],
     "tulip_range_to_xyz_durlar": [P, P, P, P, F, F, D, I, I, P, P],
     "tulip_voxel_metrics": [P, L, P, L, I, D, P, P, L, P, P, P],

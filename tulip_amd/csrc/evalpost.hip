@@ -90,6 +90,124 @@ __global__ __launch_bounds__(256) void post_final_kernel(const double* __restric
     if (threadIdx.x == 0) { out[0] = (float)(s0 * inv_all); out[1] = (float)(s1 * inv_low); }
 }
 
+// ------------------------------------------------------------------ the same for C = 2..4 planes (tulip_amd/eval_channels.py)
+// A thread owns a pixel and walks its C planes (every plane access is coalesced across the wave).  Channel 0 is post_kernel's
+// chain expression for expression; its gate / hole / valid / keep_close decisions are taken once and reused by the other planes.
+constexpr int CMAX = 4;    // in_chans of the multi-channel entry points: 2..CMAX
+
+// MC-dropout aggregate of (T, C, n): channel 0 is mc_aggregate_kernel's expression and decides the drop for all C channels
+template <int C>
+__global__ __launch_bounds__(256) void mc_aggregate_c_kernel(const float* __restrict__ preds, int T, int64_t n, float thr,
+                                                             float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += (double)preds[(int64_t)t * C * n + i];
+        const double mean = s / T;
+        double q = 0.0;
+        for (int t = 0; t < T; ++t) { const double d = (double)preds[(int64_t)t * C * n + i] - mean; q += d * d; }
+        const float mf = (float)mean;
+        const float sd = (float)sqrt(q / (double)(T - 1));
+        const bool drop = sd > thr * mf;
+        out[i] = drop ? 0.f : mf;
+#pragma unroll
+        for (int c = 1; c < C; ++c) {
+            double sc = 0.0;
+            for (int t = 0; t < T; ++t) sc += (double)preds[((int64_t)t * C + c) * n + i];
+            out[(int64_t)c * n + i] = drop ? 0.f : (float)(sc / T);
+        }
+    }
+}
+
+struct PostArgsC {
+    PostArgs a;            // pred/hi (C,H,W), lo (C,h,w), pred_img/hi_img (C,H,W)
+    int64_t lo_plane;      // h*w
+    uint32_t chan_log;     // bit c-1: channel c is stored as log1p
+};
+// partials[block][3*C+1] = {sum|p-t| per channel, sum|p-l| over the restored rows per channel, sum|p-t| over the valid target
+// pixels per channel, number of valid target pixels}
+template <int C>
+__global__ __launch_bounds__(256) void post_c_kernel(PostArgsC pa, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const PostArgs& a = pa.a;
+    const int64_t n = (int64_t)a.H * a.W;
+    double e_all[C], e_low[C], e_val[C], n_val = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) e_all[c] = e_low[c] = e_val[c] = 0.0;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
+        const int i = (int)(k / a.W), j = (int)(k - (int64_t)i * a.W);
+        float p = a.pred[k], t = a.hi[k];
+        if (a.logt) { p = expm1f(p); t = expm1f(t); }
+        p = (p >= a.gmin && p <= a.gmax) ? p : 0.f;
+        const bool hole = p == 0.f;                       // after the gate, before the rows are restored: true for -0.0 and a NaN
+        const bool valid = t > 0.f;                       // false for a NaN
+        const bool restore = a.restore_rows && i % a.f == 0;
+        const int64_t kl = restore ? (int64_t)(i / a.f) * a.W + j : 0;
+        const float d0 = fabsf(p - t);
+        e_all[0] += (double)d0;
+        if (valid) { e_val[0] += (double)d0; n_val += 1.0; }
+        if (restore) {
+            float l = a.lo[kl];
+            if (a.logt) l = expm1f(l);
+            e_low[0] += (double)fabsf(p - l);
+            p = l;
+        }
+        bool zero_p = false, zero_t = false;
+        if (a.keep_close > 0.f) {
+            zero_p = p > a.keep_close;
+            zero_t = t > a.keep_close;
+            if (zero_p) p = 0.f;
+            if (zero_t) t = 0.f;
+        }
+        a.pred_img[k] = p;
+        a.hi_img[k] = t;
+#pragma unroll
+        for (int c = 1; c < C; ++c) {
+            const bool lg = (pa.chan_log >> (c - 1)) & 1u;
+            float pc = a.pred[(int64_t)c * n + k], tc = a.hi[(int64_t)c * n + k];
+            if (lg) { pc = expm1f(pc); tc = expm1f(tc); }
+            pc = hole ? 0.f : pc;                         // a select: a NaN or an infinity in a hole yields +0.0
+            const float d = fabsf(pc - tc);
+            e_all[c] += (double)d;
+            if (valid) e_val[c] += (double)d;
+            if (restore) {
+                float l = a.lo[(int64_t)c * pa.lo_plane + kl];
+                if (lg) l = expm1f(l);
+                e_low[c] += (double)fabsf(pc - l);
+                pc = l;
+            }
+            if (zero_p) pc = 0.f;
+            if (zero_t) tc = 0.f;
+            a.pred_img[(int64_t)c * n + k] = pc;
+            a.hi_img[(int64_t)c * n + k] = tc;
+        }
+    }
+    double* out = partials + (int64_t)blockIdx.x * (3 * C + 1);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const double s0 = block_sum_d(e_all[c], red), s1 = block_sum_d(e_low[c], red), s2 = block_sum_d(e_val[c], red);
+        if (threadIdx.x == 0) { out[c] = s0; out[C + c] = s1; out[2 * C + c] = s2; }
+    }
+    n_val = block_sum_d(n_val, red);
+    if (threadIdx.x == 0) out[3 * C] = n_val;
+}
+// metrics = {mae_all[C], mae_low[C], mae_valid[C], n_valid}: float32(sum * inv); no valid pixel: mae_valid = 0
+__global__ __launch_bounds__(256) void post_c_final_kernel(const double* __restrict__ partials, int nb, int C, double inv_all,
+                                                           double inv_low, float* __restrict__ out) {
+    __shared__ double red[4];
+    const int S = 3 * C + 1;
+    double nv = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) nv += partials[(int64_t)i * S + 3 * C];
+    nv = block_sum_d(nv, red);                            // thread 0 holds it
+    if (threadIdx.x == 0) out[3 * C] = (float)nv;
+    const double inv_val = nv > 0.0 ? 1.0 / nv : 0.0;
+    for (int s = 0; s < 3 * C; ++s) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < nb; i += 256) v += partials[(int64_t)i * S + s];
+        v = block_sum_d(v, red);
+        if (threadIdx.x == 0) out[s] = (float)(v * (s < C ? inv_all : s < 2 * C ? inv_low : inv_val));
+    }
+}
+
 // ------------------------------------------------------------------ range image -> xyz
 // KITTI / CARLA (evaluation.py:52-116): products only, in the reference's order, so float32 results are bit exact
 __global__ __launch_bounds__(256) void xyz_spherical_kernel(const float* __restrict__ img, const float* __restrict__ sh,
@@ -360,6 +478,42 @@ extern "C" int tulip_eval_postprocess(const float* pred, const float* hi, const 
     hipLaunchKernelGGL(post_kernel, dim3(nb), dim3(256), 0, stream, a, partials);
     hipLaunchKernelGGL(post_final_kernel, dim3(1), dim3(256), 0, stream, partials, nb, 1.0 / ((double)H * W),
                        a.restore_rows ? 1.0 / ((double)h * W) : 0.0, mae_out);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_mc_aggregate_c(const float* preds, int passes, int C, int64_t n, float noise_threshold, float* out,
+                                    hipStream_t stream) {
+    if (!preds || !out || passes < 2 || n <= 0 || C < 2 || C > CMAX) return TULIP_ERR_ARG;
+    const dim3 grid(blocks_for(n, 4096)), block(256);
+    if (C == 2) hipLaunchKernelGGL(mc_aggregate_c_kernel<2>, grid, block, 0, stream, preds, passes, n, noise_threshold, out);
+    else if (C == 3) hipLaunchKernelGGL(mc_aggregate_c_kernel<3>, grid, block, 0, stream, preds, passes, n, noise_threshold, out);
+    else hipLaunchKernelGGL(mc_aggregate_c_kernel<4>, grid, block, 0, stream, preds, passes, n, noise_threshold, out);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+extern "C" int tulip_eval_postprocess_c(const float* pred, const float* hi, const float* lo, float* pred_img,
+                                        float* hi_img, double* partials, float* metrics, int H, int W, int h, int w, int C,
+                                        int log_transform, uint32_t chan_log_bits, float gate_min, float gate_max,
+                                        float keep_close, hipStream_t stream) {
+    if (!pred || !hi || !lo || !pred_img || !hi_img || !partials || !metrics || H <= 0 || W <= 0 || h <= 0 || w <= 0 ||
+        H % h || C < 2 || C > CMAX || (chan_log_bits >> (C - 1)))
+        return TULIP_ERR_ARG;
+    PostArgsC pa;
+    PostArgs& a = pa.a;
+    a.pred = pred; a.hi = hi; a.lo = lo; a.pred_img = pred_img; a.hi_img = hi_img;
+    a.H = H; a.W = W; a.h = h; a.f = H / h; a.restore_rows = (w == W); a.logt = log_transform;
+    a.gmin = gate_min; a.gmax = gate_max; a.keep_close = keep_close;
+    pa.lo_plane = (int64_t)h * w;
+    pa.chan_log = chan_log_bits;
+    const int nb = blocks_for((int64_t)H * W);
+    const dim3 grid(nb), block(256);
+    if (C == 2) hipLaunchKernelGGL(post_c_kernel<2>, grid, block, 0, stream, pa, partials);
+    else if (C == 3) hipLaunchKernelGGL(post_c_kernel<3>, grid, block, 0, stream, pa, partials);
+    else hipLaunchKernelGGL(post_c_kernel<4>, grid, block, 0, stream, pa, partials);
+    hipLaunchKernelGGL(post_c_final_kernel, dim3(1), dim3(256), 0, stream, partials, nb, C, 1.0 / ((double)H * W),
+                       a.restore_rows ? 1.0 / ((double)h * W) : 0.0, metrics);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }

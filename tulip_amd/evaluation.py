@@ -9,11 +9,16 @@ read back once at the end of the loop.  `evaluate` / `MCdrop` keep the reference
 files and its quirks (MCdrop's KITTI gate starts at 0, `keep_close_scan` applies to DurLAR in `evaluate` and to
 KITTI in `MCdrop`, MCdrop's results file only carries mae and chamfer_dist).  Plot/tensorboard/.ply side
 outputs are not produced.  No CPU fallback: the HIP library is required.
+
+Models with in_chans 2..4 ([range, intensity, ...]): `ChannelEvaluator`, `evaluate_multichannel`, `MCdrop_multichannel` and
+`mc_aggregate_channels` below.  The reference evaluates one channel only, so their definition is this project's
+(tulip_amd/eval_channels.py): channel 0 is evaluated exactly as above, the other channels add per-channel MAE columns.
 """
 from __future__ import annotations
 
 import json
 import math
+import numbers
 import os
 from typing import Optional
 
@@ -137,21 +142,29 @@ class RangeEvaluator:
         pred, lo, hi = pred.contiguous(), lo.contiguous(), hi.contiguous()
         ops.eval_postprocess(pred, hi, lo, self.pred_img, self.hi_img, self.scratch, self.mae, H, W, self.h, self.w,
                              self.log_transform, self.gate[0], self.gate[1], self.keep_close)
-        R = MAX_RANGE[self.ds]
-        for img, pcd in ((self.pred_img, self.pcd_pred), (self.hi_img, self.pcd_gt)):
+        self._project(self.pred_img, self.hi_img)
+
+    def _project(self, pred_img, hi_img):
+        """the two (H,W) range images -> self.pcd_pred / self.pcd_gt"""
+        H, W, R = self.H, self.W, MAX_RANGE[self.ds]
+        for img, pcd in ((pred_img, self.pcd_pred), (hi_img, self.pcd_gt)):
             if self.f64:
                 ops.range_to_xyz_durlar(img, self.colt, self.rowt, self.row_offset, R, DURLAR_ORIGIN_OFFSET,
                                         DURLAR_Z_OFFSET, H, W, pcd)
             else:
                 ops.range_to_xyz(img, *self.tables, R, H, W, pcd)
 
-    def __call__(self, pred: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
-        self.point_clouds(pred, lo, hi)
+    def _cloud_metrics(self):
+        """voxel metrics and Chamfer of self.pcd_pred / self.pcd_gt: the columns after mae and mae_low_res"""
         n = self.H * self.W
         ops.voxel_metrics(self.pcd_pred, n, self.pcd_gt, n, self.f64, self.grid_size, self.bm_pred, self.bm_gt,
                           self.bitmap_words, self.scratch, self.vox)
         ops.chamfer_sq(self.pcd_gt, n, self.pcd_pred, n, self.f64, self.dist_a, self.dist_b, self.scratch, self.cd)
-        return torch.cat([self.mae.double(), self.cd, self.vox[:4], self.vox[7:8]])
+        return [self.cd, self.vox[:4], self.vox[7:8]]
+
+    def __call__(self, pred: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+        self.point_clouds(pred, lo, hi)
+        return torch.cat([self.mae.double()] + self._cloud_metrics())
 
 
 def mc_aggregate(preds: torch.Tensor, noise_threshold: float) -> torch.Tensor:
@@ -164,6 +177,86 @@ def mc_aggregate(preds: torch.Tensor, noise_threshold: float) -> torch.Tensor:
     return out
 
 
+def channel_columns(in_chans: int):
+    """The columns a ChannelEvaluator returns after RESULT_COLUMNS (tulip_amd/eval_channels.py defines them)."""
+    cols = []
+    for c in range(1, int(in_chans)):
+        cols += [f"mae_ch{c}", f"mae_low_res_ch{c}", f"mae_valid_ch{c}"]
+    return tuple(cols) + ("mae_valid", "n_valid")
+
+
+def _check_channels(in_chans, channel_log):
+    """(C, the C-1 log flags) of a multi-channel evaluation; ValueError before any device use"""
+    if isinstance(in_chans, (bool, np.bool_)) or not isinstance(in_chans, numbers.Integral):
+        raise ValueError(f"in_chans must be an int in 2..4, got {in_chans!r}")
+    if in_chans == 1:
+        raise ValueError("in_chans == 1 is the range-image evaluation: use RangeEvaluator / evaluate / MCdrop")
+    if not 2 <= in_chans <= 4:
+        raise ValueError(f"in_chans must be an int in 2..4, got {in_chans!r}")
+    C = int(in_chans)
+    if channel_log is None:
+        return C, (False,) * (C - 1)
+    if isinstance(channel_log, (str, bytes)) or not hasattr(channel_log, "__len__"):
+        raise ValueError(f"channel_log must be a sequence of {C - 1} bools, got {channel_log!r}")
+    logs = list(channel_log)
+    if len(logs) != C - 1:
+        raise ValueError(f"in_chans={C} takes {C - 1} channel_log entries (channels 1..{C - 1}), got {len(logs)}")
+    for v in logs:
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"channel_log must hold bools, got {v!r}")
+    return C, tuple(bool(v) for v in logs)
+
+
+class ChannelEvaluator(RangeEvaluator):
+    """RangeEvaluator for images of in_chans = 2..4 channels ([range, intensity, ...]; tulip_amd/eval_channels.py is the
+    definition).  `__call__(pred (1,C,H,W), lo (1,C,h,w), hi (1,C,H,W))` returns a device float64 tensor: RESULT_COLUMNS, computed
+    from the channel-0 planes exactly as RangeEvaluator computes them, then channel_columns(C).  channel_log: the C-1 log flags of
+    channels 1..C-1, as in RangePrep(channel_log=...).  pred_img / hi_img are (C,H,W)."""
+
+    def __init__(self, dataset_select: str, img_size_low_res, img_size_high_res, log_transform: bool, in_chans: int,
+                 channel_log=None, grid_size: float = 0.1, keep_close_scan: bool = False, mc_drop: bool = False, device="cuda"):
+        self.in_chans, self.channel_log = _check_channels(in_chans, channel_log)
+        super().__init__(dataset_select, img_size_low_res, img_size_high_res, log_transform, grid_size, keep_close_scan, mc_drop,
+                         device)
+        C, dev = self.in_chans, self.device
+        del self.mae            # the single-channel launch's two MAE words: here mae and mae_low_res are metrics[0] and metrics[C]
+        self.pred_img = torch.empty(C, self.H, self.W, dtype=torch.float32, device=dev)
+        self.hi_img = torch.empty(C, self.H, self.W, dtype=torch.float32, device=dev)
+        self.partials = torch.zeros((3 * C + 1) * 1024, dtype=torch.float64, device=dev)
+        self.metrics = torch.zeros(3 * C + 1, dtype=torch.float32, device=dev)      # mae[C], mae_low_res[C], mae_valid[C], n_valid
+        self.columns = RESULT_COLUMNS + channel_columns(C)
+        self._head = torch.tensor([0, C], device=dev)
+        self._tail = torch.tensor([k * C + c for c in range(1, C) for k in range(3)] + [2 * C, 3 * C], device=dev)
+
+    def point_clouds(self, pred, lo, hi):
+        """post-processing of all C channels + projection of channel 0: fills self.pred_img/hi_img/pcd_pred/pcd_gt/metrics"""
+        C, H, W = self.in_chans, self.H, self.W
+        for t, shp in ((pred, (H, W)), (hi, (H, W)), (lo, (self.h, self.w))):
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != C * shp[0] * shp[1]:
+                raise ValueError(f"expected a float32 device tensor with {C}x{shp[0]}x{shp[1]} elements (one image)")
+        pred, lo, hi = pred.contiguous(), lo.contiguous(), hi.contiguous()
+        ops.eval_postprocess_c(pred, hi, lo, self.pred_img, self.hi_img, self.partials, self.metrics, H, W, self.h, self.w, C,
+                               self.log_transform, self.channel_log, self.gate[0], self.gate[1], self.keep_close)
+        self._project(self.pred_img[0], self.hi_img[0])
+
+    def __call__(self, pred: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+        self.point_clouds(pred, lo, hi)
+        m = self.metrics.double()
+        return torch.cat([m[self._head]] + self._cloud_metrics() + [m[self._tail]])
+
+
+def mc_aggregate_channels(preds: torch.Tensor, noise_threshold: float) -> torch.Tensor:
+    """(passes,C,H,W) -> (1,C,H,W), C = 2..4: the per-channel mean; channel 0 (mc_aggregate of it, bit for bit) decides the drop,
+    and a dropped pixel is 0 in all C channels."""
+    if preds.dtype != torch.float32 or not preds.is_cuda or preds.dim() != 4:
+        raise ValueError("preds must be a (passes,C,H,W) float32 device tensor")
+    preds = preds.contiguous()
+    T, C, H, W = preds.shape
+    out = torch.empty((1, C, H, W), dtype=torch.float32, device=preds.device)
+    ops.mc_aggregate_c(preds, T, C, H * W, noise_threshold, out)
+    return out
+
+
 def _samples(batch):
     lo, hi = batch
     if isinstance(lo, dict):
@@ -171,9 +264,18 @@ def _samples(batch):
     return lo, hi
 
 
+def _read_back(table, width: int):
+    """the one read-back of a loop: its per-image device rows as a host (images, width) float64 array"""
+    return torch.stack(table).cpu().numpy() if table else np.zeros((0, width))
+
+
 def _finish(table, args, log_writer, file_name: str, keys):
     """results file (engine:330-334 / :590-594) + the averages the loops log (engine:340-347)."""
-    res = torch.stack(table).cpu().numpy() if table else np.zeros((0, len(RESULT_COLUMNS)))
+    return _finish_rows(_read_back(table, len(RESULT_COLUMNS)), args, log_writer, file_name, keys)
+
+
+def _finish_rows(res, args, log_writer, file_name: str, keys):
+    """_finish of the rows already on the host; columns past RESULT_COLUMNS are not looked at"""
     col = {k: res[:, i] for i, k in enumerate(RESULT_COLUMNS)}
     evaluation_metrics = {k: (col[k].tolist() if k in keys else [])
                           for k in ("mae", "chamfer_dist", "iou", "precision", "recall", "f1")}
@@ -184,7 +286,7 @@ def _finish(table, args, log_writer, file_name: str, keys):
         with open(path, "w") as file:
             json.dump(evaluation_metrics, file)
         print(f"Dictionary saved to {path}")
-    n = max(len(table), 1)
+    n = max(res.shape[0], 1)
     avg = {"loss": float(col["mae"].sum() / n), "iou": float(col["iou"].sum() / n),
            "cd": float(col["chamfer_dist"].sum() / n), "f1": float(col["f1"].sum() / n),
            "precision": float(col["precision"].sum() / n), "recall": float(col["recall"].sum() / n),
@@ -254,3 +356,80 @@ def MCdrop(data_loader, model, device, log_writer=None, args=None):
         pred = mc_aggregate(preds, args.noise_threshold)
         table.append(ev(pred, lo, hi))
     return _finish(table, args, log_writer, "results_mcdrop.txt", ("mae", "chamfer_dist"))
+
+
+# ---- the same loops for a model with in_chans 2..4 (ChannelEvaluator; tulip_amd/eval_channels.py)
+def _require_channel_model(model) -> int:
+    c = getattr(model, "in_chans", 1)
+    if c == 1:
+        raise ValueError("evaluate_multichannel / MCdrop_multichannel need in_chans 2..4; this model has in_chans 1: use "
+                         "evaluate / MCdrop")
+    return c
+
+
+def _channel_evaluator(model, args, mc_drop: bool, device):
+    return ChannelEvaluator(args.dataset_select, args.img_size_low_res, args.img_size_high_res, args.log_transform,
+                            _require_channel_model(model), getattr(args, "channel_log", None), args.grid_size,
+                            getattr(args, "keep_close_scan", False), mc_drop, device)
+
+
+def _finish_channels(table, ev, args, log_writer, file_name: str, keys):
+    """_finish on the channel-0 columns (the reference's file, unchanged) + a second file `<name>_channels.txt` with one list per
+    channel_columns key; the returned dict gains the averages of those columns and `per_image_channels`."""
+    rows = _read_back(table, len(ev.columns))
+    avg = _finish_rows(rows, args, log_writer, file_name, keys)
+    cols = ev.columns[len(RESULT_COLUMNS):]
+    res = rows[:, len(RESULT_COLUMNS):]
+    per_image = {k: res[:, i].tolist() for i, k in enumerate(cols)}
+    out_dir = getattr(args, "output_dir", None)
+    if out_dir:
+        path = os.path.join(out_dir, file_name.replace(".txt", "_channels.txt"))
+        with open(path, "w") as file:
+            json.dump(per_image, file)
+        print(f"Dictionary saved to {path}")
+    n = max(rows.shape[0], 1)
+    for i, k in enumerate(cols):
+        avg[k] = float(res[:, i].sum() / n)
+    avg["per_image_channels"] = per_image
+    return avg
+
+
+@torch.no_grad()
+def evaluate_multichannel(data_loader, model, device, log_writer=None, args=None):
+    """`evaluate` for a model with in_chans 2..4: results.txt as `evaluate` writes it (from channel 0) and results_channels.txt;
+    `args.channel_log` (optional): the log flags of channels 1..C-1, as given to RangePrep."""
+    ev = _channel_evaluator(model, args, False, device)
+    model.eval()
+    table = []
+    for batch in data_loader:
+        lo, hi = _samples(batch)
+        lo = lo.to(device, non_blocking=True).float()
+        hi = hi.to(device, non_blocking=True).float()
+        pred, _, _ = model(lo, hi, eval=True)
+        for b in range(pred.shape[0]):
+            table.append(ev(pred[b:b + 1], lo[b:b + 1], hi[b:b + 1]))
+    return _finish_channels(table, ev, args, log_writer, "results.txt",
+                            ("mae", "chamfer_dist", "iou", "precision", "recall", "f1"))
+
+
+@torch.no_grad()
+def MCdrop_multichannel(data_loader, model, device, log_writer=None, args=None):
+    """`MCdrop` for a model with in_chans 2..4: the passes are aggregated by mc_aggregate_channels (channel 0 decides the drop of a
+    pixel, all C channels of it go); results_mcdrop.txt as `MCdrop` writes it and results_mcdrop_channels.txt."""
+    ev = _channel_evaluator(model, args, True, device)
+    iteration, iteration_batch = args.num_mcdropout_iterations, 8
+    assert iteration > iteration_batch
+    model.eval()
+    enable_dropout(model)
+    table = []
+    for batch in data_loader:
+        lo, hi = _samples(batch)
+        lo = lo.to(device, non_blocking=True).float()
+        hi = hi.to(device, non_blocking=True).float()
+        preds = torch.empty((iteration,) + tuple(hi.shape[1:]), dtype=torch.float32, device=device)
+        for i in range(int(np.ceil(iteration / iteration_batch))):
+            nb = min(iteration_batch, iteration - i * iteration_batch)
+            preds[i * iteration_batch:i * iteration_batch + nb] = model(lo.tile(nb, 1, 1, 1), hi, mc_drop=True)
+        pred = mc_aggregate_channels(preds, args.noise_threshold)
+        table.append(ev(pred, lo, hi))
+    return _finish_channels(table, ev, args, log_writer, "results_mcdrop.txt", ("mae", "chamfer_dist"))

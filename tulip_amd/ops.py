@@ -580,6 +580,22 @@ def eval_postprocess(pred, hi, lo, pred_img, hi_img, partials, mae_out, H, W, h,
                                              float(gate_max), float(keep_close), _stream()), "tulip_eval_postprocess")
 
 
+def mc_aggregate_c(preds, passes, C, n, noise_threshold, out):
+    """tulip_mc_aggregate_c: preds (passes, C, n) -> out (C, n); channel 0 decides the drop for all C channels."""
+    check(_lib.load().tulip_mc_aggregate_c(_p(preds), passes, int(C), n, float(noise_threshold), _p(out), _stream()),
+          "tulip_mc_aggregate_c")
+
+
+def eval_postprocess_c(pred, hi, lo, pred_img, hi_img, partials, metrics, H, W, h, w, C, log_transform, chan_log, gate_min,
+                       gate_max, keep_close):
+    """tulip_eval_postprocess_c: eval_postprocess for (C,H,W) images (tulip_amd/eval_channels.py is the host definition).
+    chan_log: the C-1 log flags of channels 1..C-1; metrics: 3*C+1 floats; partials: (3*C+1)*1024 doubles."""
+    mask = sum(1 << k for k, on in enumerate(chan_log) if on)
+    check(_lib.load().tulip_eval_postprocess_c(_p(pred), _p(hi), _p(lo), _p(pred_img), _p(hi_img), _p(partials), _p(metrics),
+                                               H, W, h, w, int(C), int(log_transform), mask, float(gate_min), float(gate_max),
+                                               float(keep_close), _stream()), "tulip_eval_postprocess_c")
+
+
 def range_to_xyz(img, sin_h, cos_h, sin_v, cos_v, max_range, H, W, xyz):
     check(_lib.load().tulip_range_to_xyz(_p(img), _p(sin_h), _p(cos_h), _p(sin_v), _p(cos_v), float(max_range), H, W,
                                          _p(xyz), _stream()), "tulip_range_to_xyz")

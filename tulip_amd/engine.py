@@ -61,6 +61,29 @@ class BlockSpec:
     idx: int = -1   # position in TulipEngine.blocks (element-dropout site numbers 1 + 4 idx + kind)
 
 
+# a block's four Linears, in the order their weight gradients leave the backward: descriptor / table name -> module path
+_LINEARS = {"fc2": "mlp.fc2", "fc1": "mlp.fc1", "proj": "attn.proj", "qkv": "attn.qkv"}
+# the activations a block's forward leaves for its backward: tulip_swin96_desc field -> Plan buffer suffix
+_FWD_ACTS = {"x1": ".x1", "xn1": ".xn1", "qkv": ".qkv", "attn_out": ".o", "xn2": ".xn2", "fc1_pre": ".h", "fc1_act": ".g",
+             "mean1": ".mean1", "rstd1": ".rstd1", "mean2": ".mean2", "rstd2": ".rstd2"}
+
+
+@dataclass(frozen=True)
+class Route:
+    """How one block runs at one batch size (TulipEngine._route).  A family is "deep" (four sliced launches, csrc/swind.hip),
+    "wide" (csrc/swinw.hip), "c96" (csrc/swin96.hip) or "seq" (the GEMM / attention sequence); the forward's and the backward's
+    are chosen independently.  The flags below say what the knobs and the geometry say, whatever family runs."""
+    fwd: str
+    bwd: str
+    drop: bool          # an element-dropout site of the block is active: the sequence both ways
+    hgrad96: bool       # C = 96: fc1_pre carries gelu'(h) from the fused forward to the fused backward ...
+    hgrad_wide: bool    # ... C = 192 / 384 ...
+    hgrad: bool         # ... any width: bit 2 of the fused launches' `masked` (the deep form always hands it over)
+    lean: bool          # C = 96: the forward does not write qkv / the fc1 pre-activation, the backward recomputes them
+    split_fwd: bool     # wide: ask for the two-workgroups-per-window form (it runs where tulip_swinw_split_bytes says it exists)
+    split_bwd: bool
+
+
 class FlatParams:
     """Flat fp32 master + bf16 shadow + address book, ordered by backward completion."""
 
@@ -558,8 +581,8 @@ class TulipEngine:
         if B not in self.plans:
             self.plans[B] = Plan(self, B)
             # block widths this batch size runs fused: their weight copies are maintained from now on
-            widths = {sp.C for sp in self.blocks if ((self.fuse_wide or self.fuse_wide_bwd) and self._fusable_wide(sp, B))
-                      or self._fusable_deep(sp, B)}
+            streams = lambda r: r.fwd in ("wide", "deep") or r.bwd in ("wide", "deep")
+            widths = {sp.C for sp in self.blocks if streams(self._route(sp, B, drop=False))}
             if not widths <= self.params.pk_active:
                 self.params.pk_active |= widths
                 self.params.pack_epoch += 1
@@ -616,17 +639,16 @@ class TulipEngine:
     fc1_grad96 = knobs.on("TULIP_FC1_GRAD", True)
 
     def _hgrad96(self, sp: BlockSpec) -> bool:
-        return (self.fc1_grad96 and self.fuse_block96 and self.fuse_block96_bwd and self._fusable96(sp)
-                and not self._recomp96(sp))
+        return self._route(sp).hgrad96
 
     # ... and the same hand-off in the fused wide blocks (csrc/swinw.hip): TULIP_FC1_GRAD_WIDE=0 switches it off there
     fc1_grad_wide = knobs.on("TULIP_FC1_GRAD_WIDE", True)
 
     def _hgrad_wide(self, sp: BlockSpec, B: int) -> bool:
-        return self.fc1_grad_wide and self.fuse_wide and self.fuse_wide_bwd and self._fusable_wide(sp, B)
+        return self._route(sp, B).hgrad_wide
 
     def _recomp96(self, sp: BlockSpec) -> bool:
-        return self.recompute96 and self.fuse_block96 and self.fuse_block96_bwd and self._fusable96(sp)
+        return self._route(sp).lean
 
     def _fusable96(self, sp: BlockSpec) -> bool:
         """csrc/swin96.hip covers the embed-width-96 block: 3 heads x 32, window 2x8, MLP 96 -> 384 -> 96."""
@@ -648,7 +670,8 @@ class TulipEngine:
         """`masked` argument of the attention / block kernels: bit 0 shifted-window mask, bit 1 fp8 scores, bit 2 (fused
         blocks, TULIP_BLOCK_FC1_GRAD; B = the plan's batch size for the wide ones) the fc1_pre buffer carries gelu'(h) from
         the forward to the backward."""
-        hg = self._hgrad96(sp) or (B is not None and (self._hgrad_wide(sp, B) or self._fusable_deep(sp, B)))
+        r = self._route(sp, B)
+        hg = r.hgrad96 if B is None else r.hgrad         # (without B: the sequence's attention launches, the C = 96 bit alone)
         return int(bool(sp.shift)) | (2 if self.attn_fp8 else 0) | (4 if hg else 0) | (8 if self.no_warm else 0)
 
     # two workgroups per window for the C = 384 blocks where one workgroup owns one window (csrc/swinw.hip, SPLIT)
@@ -692,11 +715,26 @@ class TulipEngine:
             ok = self.deep_min_windows <= B * (sp.H // sp.win[0]) * (sp.W // sp.win[1]) <= self.deep_max_windows
         return ok
 
+    def _route(self, sp: BlockSpec, B: Optional[int] = None, drop: Optional[bool] = None) -> Route:
+        """The one place that decides how a block runs: a pure function of the knobs above, the forward's state (_drop, _no_save),
+        the block and the plan's batch size -- never cached: tests, tools and the Trainer set the knobs on a live engine.
+        B = None: as the geometry predicates read it (could the block ever ...; what concerns a C = 96 block does not depend on B).
+        drop: the block's dropout state, where not the current forward's (plan(): copies are kept whatever it is at the moment)."""
+        drop = self._dblock(sp) if drop is None else drop
+        c96, wide, deep = self._fusable96(sp), self._fusable_wide(sp, B), self._fusable_deep(sp, B)
+        both96, both_wide = self.fuse_block96 and self.fuse_block96_bwd and c96, self.fuse_wide and self.fuse_wide_bwd and wide
+        lean = bool(self.recompute96 and both96)
+        hgrad96, hgrad_wide = bool(self.fc1_grad96 and both96 and not lean), bool(self.fc1_grad_wide and both_wide)
+        fwd = ("seq" if drop else "deep" if deep else "wide" if (self.fuse_wide and wide)
+               else "c96" if (self.fuse_block96 and c96) else "seq")
+        bwd = ("seq" if drop else "deep" if deep else "c96" if (self.fuse_block96_bwd and c96)
+               else "wide" if (self.fuse_wide_bwd and wide) else "seq")
+        return Route(fwd, bwd, drop, hgrad96, hgrad_wide, hgrad96 or hgrad_wide or deep, lean,
+                     split_fwd=bool(fwd == "wide" and self.split_wide and (self._no_save or hgrad_wide)),
+                     split_bwd=bool(bwd == "wide" and self.split_wide_bwd and hgrad_wide))
+
     def _fused_bwd(self, sp: BlockSpec, B: int) -> bool:
-        if self._dblock(sp):
-            return False
-        return ((self.fuse_block96_bwd and self._fusable96(sp)) or (self.fuse_wide_bwd and self._fusable_wide(sp, B))
-                or self._fusable_deep(sp, B))
+        return self._route(sp, B).bwd != "seq"
 
     fuse_splitk_ln = True
     fuse_tail_bwd = True      # head backward without the d(expand) tensor
@@ -704,10 +742,7 @@ class TulipEngine:
     _tail_fused = False
 
     def _unfused(self, sp: BlockSpec, B: int) -> bool:
-        if self._dblock(sp):
-            return True
-        return not ((self.fuse_wide and self._fusable_wide(sp, B)) or (self.fuse_block96 and self._fusable96(sp))
-                    or self._fusable_deep(sp, B))
+        return self._route(sp, B).fwd == "seq"
 
     # ------------------------------------------------------------------ element dropout
     # A site is active iff its nn.Dropout has p > 0 and is in training mode (the torch rule: model.eval() followed by switching the
@@ -753,44 +788,43 @@ class TulipEngine:
                    rowscale=rowscale, rows_per_sample=tok, out2=out2, ldo2=N if out2 is not None else 0)
         ops.layernorm_fwd(out, gamma, beta, xn, mean, rstd, M, N, self.eps)
 
+    def _fwd_desc(self, P: Plan, sp: BlockSpec, xin, xout, wf, saved=None) -> dict:
+        """The fields of tulip_swin96_desc for one block, whichever kernel family takes them.  wf: where the kernel reads its bf16
+        weights (params.p16: the shadow, p16p: the fragment-major copies); saved: the activations (Plan buffer suffixes) the
+        launch writes, None = all of them -- the others are NULL."""
+        W_, p = self.params, sp.prefix
+        d = {f: P[p + k] if (saved is None or k in saved) else None for f, k in _FWD_ACTS.items()}
+        for n, mod in _LINEARS.items():
+            d["w_" + n], d["b_" + n] = wf(f"{p}.{mod}.weight"), W_.p32(f"{p}.{mod}.bias")
+        for n in ("norm1", "norm2"):
+            d[n + "_weight"], d[n + "_bias"] = W_.p32(f"{p}.{n}.weight"), W_.p32(f"{p}.{n}.bias")
+        d.update(x_in=xin, x_out=xout, bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
+                 drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), B=P.B, H=sp.H, W=sp.W,
+                 shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, P.B), eps=self.eps)
+        return d
+
     def _block_fwd(self, P: Plan, sp: BlockSpec, xin, xout, out_bf16=None, ln1_done=False, next_sp=None):
         """out_bf16: the block output also leaves as a bf16 [M][C] copy (operand of a PatchUnmerging GEMM).
         ln1_done: the previous (unfused) block's fc2 launch already wrote this block's xn1 / mean1 / rstd1;
         next_sp: the next block of the stage if it runs unfused too -- its norm1 then rides in this block's fc2 fold."""
-        W_ = self.params
-        p = sp.prefix
-        B, C, nh = P.B, sp.C, sp.nh
-        M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
-        drop = self._dblock(sp)                    # element dropout active in this block: the launch sequence below
-        wide = self.fuse_wide and self._fusable_wide(sp, B) and not drop
-        if self._fusable_deep(sp, B) and not drop:
+        W_, p, B, C = self.params, sp.prefix, P.B, sp.C
+        r = self._route(sp, B)
+        if r.fwd == "seq":                         # (element dropout active in this block: always)
+            self._block_fwd_seq(P, sp, xin, xout, out_bf16, ln1_done, next_sp)
+        elif r.fwd == "deep":
             # four sliced launches (csrc/swind.hip: by heads, by output channels, by hidden channels, by output channels); same
             # tensors as the sequence
             self._join_pack(p)
             keep = (".o", ".x1", ".g")              # pass from launch to launch: written in the inference form too
-            sv = (lambda k: P[p + k] if k in keep else None) if self._no_save else (lambda k: P[p + k])
-            wf = W_.p16p
-            ops.swind_block_fwd(
-                C, sp.win, out_bf16=out_bf16,
-                x_in=xin, x1=sv(".x1"), x_out=xout, xn1=sv(".xn1"), qkv=sv(".qkv"), attn_out=sv(".o"),
-                xn2=sv(".xn2"), fc1_pre=sv(".h"), fc1_act=sv(".g"), mean1=sv(".mean1"),
-                rstd1=sv(".rstd1"), mean2=sv(".mean2"), rstd2=sv(".rstd2"),
-                w_qkv=wf(p + ".attn.qkv.weight"), w_proj=wf(p + ".attn.proj.weight"),
-                w_fc1=wf(p + ".mlp.fc1.weight"), w_fc2=wf(p + ".mlp.fc2.weight"),
-                b_qkv=W_.p32(p + ".attn.qkv.bias"), b_proj=W_.p32(p + ".attn.proj.bias"),
-                b_fc1=W_.p32(p + ".mlp.fc1.bias"), b_fc2=W_.p32(p + ".mlp.fc2.bias"),
-                norm1_weight=W_.p32(p + ".norm1.weight"), norm1_bias=W_.p32(p + ".norm1.bias"),
-                norm2_weight=W_.p32(p + ".norm2.weight"), norm2_bias=W_.p32(p + ".norm2.bias"),
-                bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
-                drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), B=B, H=sp.H, W=sp.W,
-                shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, B), eps=self.eps)
-            return
-        if wide or (self.fuse_block96 and self._fusable96(sp) and not drop):
+            ops.swind_block_fwd(C, sp.win, out_bf16=out_bf16,
+                                **self._fwd_desc(P, sp, xin, xout, W_.p16p, keep if self._no_save else None))
+        else:
             # the whole block in one launch (csrc/swin96.hip, csrc/swinw.hip); writes the same tensors as the sequence below
+            wide = r.fwd == "wide"
             if wide:
                 self._join_pack(p)                 # the fragment-major weight copies being rewritten beside the forward
             xkw = {}
-            if wide and self.split_wide and (self._no_save or self._hgrad_wide(sp, B)):
+            if r.split_fwd:
                 # C = 384 with one window per workgroup: two workgroups per window (tulip_swinw_block_fwd_split)
                 nb = ops.swinw_split_bytes(C, B, sp.H, sp.W)
                 if nb:
@@ -800,60 +834,27 @@ class TulipEngine:
             wf = W_.p16p if wide else W_.p16           # the wide kernel streams fragment-major copies of the weights
             # forward without a backward behind it (run_forward(with_loss=False): eval / MC-dropout inference): the kernels'
             # inference form -- none of the activations a backward would read is written (90 % of the C = 96 kernel's traffic)
-            lean = (not wide) and self._recomp96(sp)                # qkv / fc1 pre-activation: recomputed by the backward
-            sv = (lambda k: None) if self._no_save else (lambda k: None if (lean and k in (".qkv", ".h")) else P[p + k])
-            launch(
-                x_in=xin, x1=sv(".x1"), x_out=xout, xn1=sv(".xn1"), qkv=sv(".qkv"), attn_out=sv(".o"),
-                xn2=sv(".xn2"), fc1_pre=sv(".h"), fc1_act=sv(".g"), mean1=sv(".mean1"),
-                rstd1=sv(".rstd1"), mean2=sv(".mean2"), rstd2=sv(".rstd2"),
-                w_qkv=wf(p + ".attn.qkv.weight"), w_proj=wf(p + ".attn.proj.weight"),
-                w_fc1=wf(p + ".mlp.fc1.weight"), w_fc2=wf(p + ".mlp.fc2.weight"),
-                b_qkv=W_.p32(p + ".attn.qkv.bias"), b_proj=W_.p32(p + ".attn.proj.bias"),
-                b_fc1=W_.p32(p + ".mlp.fc1.bias"), b_fc2=W_.p32(p + ".mlp.fc2.bias"),
-                norm1_weight=W_.p32(p + ".norm1.weight"), norm1_bias=W_.p32(p + ".norm1.bias"),
-                norm2_weight=W_.p32(p + ".norm2.weight"), norm2_bias=W_.p32(p + ".norm2.bias"),
-                bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
-                drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), B=B, H=sp.H, W=sp.W,
-                shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, B), eps=self.eps)
+            saved = () if self._no_save else None
+            if r.lean and saved is None:            # qkv / fc1 pre-activation: recomputed by the backward
+                saved = [k for k in _FWD_ACTS.values() if k not in (".qkv", ".h")]
+            launch(**self._fwd_desc(P, sp, xin, xout, wf, saved))
             if out_bf16 is not None and not wide:
-                ops.cast_f32_bf16(xout, out_bf16, M, C)
-            return
+                ops.cast_f32_bf16(xout, out_bf16, B * sp.H * sp.W, C)
+
+    def _block_fwd_seq(self, P: Plan, sp: BlockSpec, xin, xout, out_bf16, ln1_done, next_sp):
+        """The block's forward as the GEMM / attention sequence, with whichever element-dropout sites are active (none: every
+        `_dp` below is 0.0): attn_drop in the attention kernel, proj_drop / drop2 as a plain fp32 Linear output +
+        tulip_dropout_resid_ln (mask, DropPath scale, residual, bf16 copy and the LayerNorm behind it), drop1 in place on the GELU
+        output that fc2 and its weight gradient read."""
+        W_ = self.params
+        p = sp.prefix
+        B, C, nh = P.B, sp.C, sp.nh
+        M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
         if not ln1_done:
             ops.layernorm_fwd(xin, W_.p32(p + ".norm1.weight"), W_.p32(p + ".norm1.bias"), P[p + ".xn1"],
                               P[p + ".mean1"], P[p + ".rstd1"], M, C, self.eps)
         self._gemm(P[p + ".xn1"], W_.p16(p + ".attn.qkv.weight"), M, 3 * C, C, lda=C, ldb=C, epi=EPI_BF16,
                  bias=W_.p32(p + ".attn.qkv.bias"), out=P[p + ".qkv"])
-        if drop:
-            self._block_fwd_drop(P, sp, xin, xout, out_bf16, next_sp)
-            return
-        ops.window_attn_fwd(P[p + ".qkv"], W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, P[p + ".o"],
-                            B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp))
-        self._gemm_resid_ln(P[p + ".o"], W_.p16(p + ".attn.proj.weight"), M, C, C, lda=C, ldb=C,
-                            bias=W_.p32(p + ".attn.proj.bias"), out=P[p + ".x1"], aux=xin, rowscale=self._ds(P, sp, 0), tok=tok,
-                            ln=(W_.p32(p + ".norm2.weight"), W_.p32(p + ".norm2.bias"), P[p + ".xn2"], P[p + ".mean2"],
-                                P[p + ".rstd2"]))
-        self._gemm(P[p + ".xn2"], W_.p16(p + ".mlp.fc1.weight"), M, Hd, C, lda=C, ldb=C, epi=EPI_GELU_DUAL,
-                 bias=W_.p32(p + ".mlp.fc1.bias"), out=P[p + ".h"], out2=P[p + ".g"], ldo2=Hd)
-        if next_sp is not None:
-            q = next_sp.prefix
-            self._gemm_resid_ln(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd,
-                                bias=W_.p32(p + ".mlp.fc2.bias"), out=xout, aux=P[p + ".x1"], rowscale=self._ds(P, sp, 1),
-                                tok=tok, out2=out_bf16,
-                                ln=(W_.p32(q + ".norm1.weight"), W_.p32(q + ".norm1.bias"), P[q + ".xn1"], P[q + ".mean1"],
-                                    P[q + ".rstd1"]))
-            return
-        self._gemm(P[p + ".g"], W_.p16(p + ".mlp.fc2.weight"), M, C, Hd, lda=Hd, ldb=Hd, epi=EPI_RESID_F32,
-                 bias=W_.p32(p + ".mlp.fc2.bias"), out=xout, aux=P[p + ".x1"], ldaux=C,
-                 rowscale=self._ds(P, sp, 1), rows_per_sample=tok, out2=out_bf16, ldo2=C if out_bf16 is not None else 0)
-
-    def _block_fwd_drop(self, P: Plan, sp: BlockSpec, xin, xout, out_bf16, next_sp):
-        """The rest of an unfused block's forward (behind the qkv GEMM) with its active element-dropout sites: attn_drop in the
-        attention kernel, proj_drop / drop2 as a plain fp32 Linear output + tulip_dropout_resid_ln (mask, DropPath scale, residual,
-        bf16 copy and the LayerNorm behind it), drop1 in place on the GELU output that fc2 and its weight gradient read."""
-        W_ = self.params
-        p = sp.prefix
-        B, C, nh = P.B, sp.C, sp.nh
-        M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
         if self._dp(sp, 0):
             ops.window_attn_fwd_drop(P[p + ".qkv"], W_.p32(p + ".attn.relative_position_bias_table"), self._rel32, P[p + ".o"],
                                      B, sp.H, sp.W, C, nh, sp.win, sp.sft, self._mask_arg(sp), **self._dkw(P, sp, 0))
@@ -960,8 +961,8 @@ class TulipEngine:
                 paired, ln1_done = True, False
                 x = P[sp.prefix + ".out"]
                 continue
-            chain = (nxt is not None and self._unfused(sp, P.B) and self._unfused(nxt, P.B) and nxt.C == sp.C
-                     and nxt.H == sp.H and nxt.W == sp.W)
+            chain = (nxt is not None and self._route(sp, P.B).fwd == "seq" and self._route(nxt, P.B).fwd == "seq"
+                     and nxt.C == sp.C and nxt.H == sp.H and nxt.W == sp.W)
             self._block_fwd(P, sp, x, P[sp.prefix + ".out"], out_bf16 if k == len(specs) - 1 else None, ln1_done=ln1_done,
                             next_sp=nxt if chain else None)
             self._issue_pack()                     # (no-op unless a weight-copy refresh is waiting for the chain's next kernel)
@@ -972,32 +973,17 @@ class TulipEngine:
     def _pair96_ok(self, P: Plan, sp: BlockSpec, nxt: BlockSpec) -> bool:
         """Two consecutive C = 96 blocks as ONE launch (tulip_swin96_pair_fwd): the un-shifted block and the shifted block behind
         it, where the stage is one round of the chip (every workgroup resident: <= 256 tiles of 8 windows)."""
-        if not (self.pair96 and self.fuse_block96 and self._fusable96(sp) and self._fusable96(nxt)):
+        a, b = self._route(sp, P.B), self._route(nxt, P.B)
+        if not (self.pair96 and a.fwd == "c96" and b.fwd == "c96"):
             return False
-        if self._dblock(sp) or self._dblock(nxt):
+        if a.lean or b.lean or (nxt.H, nxt.W) != (sp.H, sp.W):
             return False
-        if self._recomp96(sp) or self._recomp96(nxt) or (nxt.H, nxt.W) != (sp.H, sp.W):
-            return False
-        if not self._no_save and not (self._hgrad96(sp) and self._hgrad96(nxt)):     # the training form built: gelu'(h) in fc1_pre
+        if not self._no_save and not (a.hgrad96 and b.hgrad96):     # the training form built: gelu'(h) in fc1_pre
             return False
         return P.B * (sp.H // 2) * (sp.W // 64) <= self.pair96_max_tiles
 
     def _desc96(self, P: Plan, sp: BlockSpec, xin, xout) -> dict:
-        W_, p = self.params, sp.prefix
-        sv = (lambda k: None) if self._no_save else (lambda k: P[p + k])
-        return dict(
-            x_in=xin, x1=sv(".x1"), x_out=xout, xn1=sv(".xn1"), qkv=sv(".qkv"), attn_out=sv(".o"),
-            xn2=sv(".xn2"), fc1_pre=sv(".h"), fc1_act=sv(".g"), mean1=sv(".mean1"),
-            rstd1=sv(".rstd1"), mean2=sv(".mean2"), rstd2=sv(".rstd2"),
-            w_qkv=W_.p16(p + ".attn.qkv.weight"), w_proj=W_.p16(p + ".attn.proj.weight"),
-            w_fc1=W_.p16(p + ".mlp.fc1.weight"), w_fc2=W_.p16(p + ".mlp.fc2.weight"),
-            b_qkv=W_.p32(p + ".attn.qkv.bias"), b_proj=W_.p32(p + ".attn.proj.bias"),
-            b_fc1=W_.p32(p + ".mlp.fc1.bias"), b_fc2=W_.p32(p + ".mlp.fc2.bias"),
-            norm1_weight=W_.p32(p + ".norm1.weight"), norm1_bias=W_.p32(p + ".norm1.bias"),
-            norm2_weight=W_.p32(p + ".norm2.weight"), norm2_bias=W_.p32(p + ".norm2.bias"),
-            bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
-            drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), B=P.B, H=sp.H, W=sp.W,
-            shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, P.B), eps=self.eps)
+        return self._fwd_desc(P, sp, xin, xout, self.params.p16, () if self._no_save else None)
 
     def _pair96_fwd(self, P: Plan, sp: BlockSpec, nxt: BlockSpec, xin):
         nb = ops.swin96_pair_sync_bytes(P.B, sp.H, sp.W)
@@ -1713,9 +1699,48 @@ class TulipEngine:
 
     def _mlp_cast(self, P: Plan, sp: BlockSpec):
         """What the producer of this block's incoming gradient should emit: (dyb_m, DropPath scale, tokens)."""
-        if self._fused_bwd(sp, P.B) or self._dblock(sp):
+        r = self._route(sp, P.B)
+        if r.bwd != "seq" or r.drop:
             return None                     # the fused block backward / a dropout block forms its own operand from the fp32 gradient
         return (P[sp.prefix + ".dyb_m"], self._ds(P, sp, 1), sp.H * sp.W)
+
+    def _bwd_desc(self, P: Plan, sp: BlockSpec, xin, dx, wt, apart, lean=False, **partials) -> dict:
+        """The fields of tulip_swin96_bwd_desc for one block.  wt: where the kernel reads its bf16 weights (params.p16: the shadow,
+        p16t: the fragment-major copies of the transposes); lean: the C = 96 kernel recomputes qkv / the fc1 pre-activation (it
+        then needs the biases the saved tensors had folded in); partials: what the one-launch forms write beside the data gradient
+        (dx_bf16, dx_bf16_scale, norm1_partials, norm2_partials)."""
+        W_, p = self.params, sp.prefix
+        d = {f: P[p + k] for f, k in _FWD_ACTS.items() if f in ("x1", "mean1", "rstd1", "mean2", "rstd2")}
+        d.update(qkv=None if lean else P[p + ".qkv"], fc1_pre=None if lean else P[p + ".h"])
+        for n, mod in _LINEARS.items():
+            d["w_" + n] = wt(f"{p}.{mod}.weight")
+        if lean:
+            d.update(b_qkv=W_.p32(p + ".attn.qkv.bias"), b_fc1=W_.p32(p + ".mlp.fc1.bias"),
+                     norm1_bias=W_.p32(p + ".norm1.bias"), norm2_bias=W_.p32(p + ".norm2.bias"))
+        d.update(dx=dx, x_in=xin, norm1_weight=W_.p32(p + ".norm1.weight"), norm2_weight=W_.p32(p + ".norm2.weight"),
+                 bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
+                 drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), d_out_mlp=P[p + ".dyb_m"],
+                 d_fc1_pre=P[p + ".dh"], d_out_attn=P[p + ".dyb_a"], d_qkv=P[p + ".dqkv"], bias_partials=apart, B=P.B, H=sp.H,
+                 W=sp.W, shift_h=sp.sft[0], shift_w=sp.sft[1], masked=self._mask_arg(sp, P.B), **partials)
+        return d
+
+    def _block_wgrads(self, P: Plan, sp: BlockSpec, G):
+        """wg(name): queue the weight and bias gradient of one of the block's Linears (_LINEARS), dW[Nw][Kw] += dY^T . X"""
+        p, C, Hd, M = sp.prefix, sp.C, self.hidden(sp.C), P.B * sp.H * sp.W
+        # name: (dY, its leading dimension, X, its leading dimension, Nw, Kw)
+        table = {"fc2": (P[p + ".dyb_m"], C, P[p + ".g"], Hd, C, Hd), "fc1": (P[p + ".dh"], Hd, P[p + ".xn2"], C, Hd, C),
+                 "proj": (P[p + ".dyb_a"], C, P[p + ".o"], C, C, C), "qkv": (P[p + ".dqkv"], 3 * C, P[p + ".xn1"], C, 3 * C, C)}
+
+        def wg(name):
+            mod = f"{p}.{_LINEARS[name]}"
+            self._wgrad(*table[name], M, G(mod + ".weight"), G(mod + ".bias"))
+        return wg
+
+    def _fire_lagged_hook(self):
+        """the end of a block's backward: bucket join + all-reduce of the previous group, one block late (run_backward)"""
+        if self._lagged_hook is not None:
+            fn, self._lagged_hook = self._lagged_hook, None
+            fn()
 
     def _block_bwd(self, P: Plan, sp: BlockSpec, xin, dx, G, have_dyb=False, next_cast=None):
         """In-place: dx (grad w.r.t. block output) -> grad w.r.t. block input.  G(name) = grad address.
@@ -1727,46 +1752,36 @@ class TulipEngine:
         M, Hd, tok = B * sp.H * sp.W, self.hidden(sp.C), sp.H * sp.W
         dxn, dO, dh, dqkv = P["t.dxn"], P["t.do"], P[p + ".dh"], P[p + ".dqkv"]
         dyb = P[p + ".dyb_m"]
-        drop = self._dblock(sp)
-        if self._fusable_deep(sp, B) and not drop:
+        r = self._route(sp, B)
+        drop = r.drop
+        wg = self._block_wgrads(P, sp, G)
+        if r.bwd == "deep":
             # csrc/swind.hip: fc2' + GELU' (by hidden channels) -> fc1' (by output channels) -> norm2' -> proj' + attention' (by heads)
             # -> qkv' (by output channels) -> norm1'; the LayerNorm backward launches are the sequence's own, fed one fp32 "slab"
             dn = P.scratch("deep.dxn", max(P.B * q.H * q.W * q.C for q in self.blocks if self._fusable_deep(q, P.B)))
             R = ops.swind_groups(C, B, sp.H, sp.W, sp.win)
             apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
-            wt = W_.p16t
-            desc = dict(
-                dx=dx, x_in=xin, x1=P[p + ".x1"], qkv=P[p + ".qkv"], fc1_pre=P[p + ".h"], mean1=P[p + ".mean1"],
-                rstd1=P[p + ".rstd1"], mean2=P[p + ".mean2"], rstd2=P[p + ".rstd2"],
-                w_qkv=wt(p + ".attn.qkv.weight"), w_proj=wt(p + ".attn.proj.weight"),
-                w_fc1=wt(p + ".mlp.fc1.weight"), w_fc2=wt(p + ".mlp.fc2.weight"),
-                norm1_weight=W_.p32(p + ".norm1.weight"), norm2_weight=W_.p32(p + ".norm2.weight"),
-                bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
-                drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), d_out_mlp=dyb, d_fc1_pre=dh,
-                d_out_attn=P[p + ".dyb_a"], d_qkv=dqkv, bias_partials=apart, B=B, H=sp.H, W=sp.W, shift_h=sp.sft[0],
-                shift_w=sp.sft[1], masked=self._mask_arg(sp, B))
+            desc = self._bwd_desc(P, sp, xin, dx, W_.p16t, apart)
             ops.swind_block_bwd(C, sp.win, dn, phases=3, **desc)
             self._release_deferred()
-            self._wgrad(dyb, C, P[p + ".g"], Hd, C, Hd, M, G(p + ".mlp.fc2.weight"), G(p + ".mlp.fc2.bias"))
-            self._wgrad(dh, Hd, P[p + ".xn2"], C, Hd, C, M, G(p + ".mlp.fc1.weight"), G(p + ".mlp.fc1.bias"))
+            wg("fc2")
+            wg("fc1")
             self._ln_bwd(P, None, P[p + ".x1"], P[p + ".mean2"], P[p + ".rstd2"], W_.p32(p + ".norm2.weight"), dx, dx, M, C,
                          G(p + ".norm2.weight"), G(p + ".norm2.bias"), p + ".2", cast=(P[p + ".dyb_a"], self._ds(P, sp, 0), tok),
                          slabs=(dn, 1))
             ops.swind_block_bwd(C, sp.win, dn, phases=12, **desc)
-            self._wgrad(P[p + ".dyb_a"], C, P[p + ".o"], C, C, C, M, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"))
+            wg("proj")
             self._fold_bias_table(P, p, apart, R, nh, G(p + ".attn.relative_position_bias_table"))
             self._ln_bwd(P, None, xin, P[p + ".mean1"], P[p + ".rstd1"], W_.p32(p + ".norm1.weight"), dx, dx, M, C,
                          G(p + ".norm1.weight"), G(p + ".norm1.bias"), p + ".1", cast=next_cast, slabs=(dn, 1))
-            self._wgrad(dqkv, 3 * C, P[p + ".xn1"], C, 3 * C, C, M, G(p + ".attn.qkv.weight"), G(p + ".attn.qkv.bias"))
-            if self._lagged_hook is not None:
-                fn, self._lagged_hook = self._lagged_hook, None
-                fn()
+            wg("qkv")
+            self._fire_lagged_hook()
             return
-        if self._fused_bwd(sp, B):
+        if r.bwd != "seq":
             # the whole data-gradient chain of the block in one launch (csrc/swin96.hip, csrc/swinw.hip); the weight
             # gradients and the folds of its per-workgroup partial rows run beside the chain exactly as for the unfused
             # sequence
-            wide = not (self.fuse_block96_bwd and self._fusable96(sp))
+            wide = r.bwd == "wide"
             cb, cs, ct = next_cast if next_cast is not None else (None, None, tok)
             if cs is not None and ct != tok:
                 raise ValueError("fused block backward: the cast scale must be per sample")
@@ -1774,41 +1789,24 @@ class TulipEngine:
             ln1, ln2 = P.scratch("lnp." + p + ".1", R * 2 * C), P.scratch("lnp." + p + ".2", R * 2 * C)
             apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
             xkw = {}
-            if wide and self.split_wide_bwd and self._hgrad_wide(sp, B):
+            if r.split_bwd:
                 nb = ops.swinw_split_bytes(C, B, sp.H, sp.W)       # two workgroups per window (tulip_swinw_block_bwd_split)
                 if nb:
                     P.scratch("xchg." + p, (nb + 3) // 4)
                     xkw["exchange"] = P.bufs["xchg." + p]
             launch = (lambda **kw: ops.swinw_block_bwd(C, **xkw, **kw)) if wide else ops.swin96_block_bwd
             wt = W_.p16t if wide else W_.p16          # the wide kernel streams fragment-major TRANSPOSED weights
-            lean = (not wide) and self._recomp96(sp)
-            extra = dict(b_qkv=W_.p32(p + ".attn.qkv.bias"), b_fc1=W_.p32(p + ".mlp.fc1.bias"),
-                         norm1_bias=W_.p32(p + ".norm1.bias"), norm2_bias=W_.p32(p + ".norm2.bias")) if lean else {}
-            launch(
-                dx=dx, x_in=xin, x1=P[p + ".x1"], qkv=None if lean else P[p + ".qkv"], fc1_pre=None if lean else P[p + ".h"],
-                mean1=P[p + ".mean1"],
-                rstd1=P[p + ".rstd1"], mean2=P[p + ".mean2"], rstd2=P[p + ".rstd2"],
-                w_qkv=wt(p + ".attn.qkv.weight"), w_proj=wt(p + ".attn.proj.weight"),
-                w_fc1=wt(p + ".mlp.fc1.weight"), w_fc2=wt(p + ".mlp.fc2.weight"),
-                norm1_weight=W_.p32(p + ".norm1.weight"), norm2_weight=W_.p32(p + ".norm2.weight"),
-                bias_table=W_.p32(p + ".attn.relative_position_bias_table"), rel_index=self._rel32,
-                drop_scale_attn=self._ds(P, sp, 0), drop_scale_mlp=self._ds(P, sp, 1), d_out_mlp=dyb, d_fc1_pre=dh,
-                d_out_attn=P[p + ".dyb_a"], d_qkv=dqkv, dx_bf16=cb, dx_bf16_scale=cs, norm1_partials=ln1,
-                norm2_partials=ln2, bias_partials=apart, B=B, H=sp.H, W=sp.W, shift_h=sp.sft[0], shift_w=sp.sft[1],
-                masked=self._mask_arg(sp, B), **extra)
+            launch(**self._bwd_desc(P, sp, xin, dx, wt, apart, lean=r.lean, dx_bf16=cb, dx_bf16_scale=cs, norm1_partials=ln1,
+                                    norm2_partials=ln2))
             self._release_deferred()
-            self._wgrad(dyb, C, P[p + ".g"], Hd, C, Hd, M, G(p + ".mlp.fc2.weight"), G(p + ".mlp.fc2.bias"))
-            self._wgrad(dh, Hd, P[p + ".xn2"], C, Hd, C, M, G(p + ".mlp.fc1.weight"), G(p + ".mlp.fc1.bias"))
-            self._wgrad(P[p + ".dyb_a"], C, P[p + ".o"], C, C, C, M, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"))
-            self._wgrad(dqkv, 3 * C, P[p + ".xn1"], C, 3 * C, C, M, G(p + ".attn.qkv.weight"), G(p + ".attn.qkv.bias"))
+            for name in _LINEARS:
+                wg(name)
             self._fold(ln2, 2 * C, G(p + ".norm2.weight"), C, R)
             self._fold(ln2 + 4 * C, 2 * C, G(p + ".norm2.bias"), C, R)
             self._fold(ln1, 2 * C, G(p + ".norm1.weight"), C, R)
             self._fold(ln1 + 4 * C, 2 * C, G(p + ".norm1.bias"), C, R)
             self._fold_bias_table(P, p, apart, R, nh, G(p + ".attn.relative_position_bias_table"))
-            if self._lagged_hook is not None:
-                fn, self._lagged_hook = self._lagged_hook, None
-                fn()
+            self._fire_lagged_hook()
             return
         # ---- MLP branch (tulip.py:346-351)
         if drop and self._dp(sp, 3):                # drop2: bf16(dx * DropPath scale * mask / (1-p))
@@ -1820,14 +1818,14 @@ class TulipEngine:
         if drop and self._dp(sp, 2):                # drop1: the mask commutes with gelu'
             ops.dropout_scale(dh, True, M, Hd, **self._dkw(P, sp, 2))
         self._release_deferred()
-        self._wgrad(dyb, C, P[p + ".g"], Hd, C, Hd, M, G(p + ".mlp.fc2.weight"), G(p + ".mlp.fc2.bias"))
+        wg("fc2")
         self._dgrad_ln_bwd(P, dh, W_.p16(p + ".mlp.fc1.weight"), M, C, Hd, dxn,
                            (P[p + ".x1"], P[p + ".mean2"], P[p + ".rstd2"], W_.p32(p + ".norm2.weight"), dx, dx, M, C,
                             G(p + ".norm2.weight"), G(p + ".norm2.bias"), p + ".2"),
                            dict(cast=None if (drop and self._dp(sp, 1)) else (P[p + ".dyb_a"], self._ds(P, sp, 0), tok)))
         if drop and self._dp(sp, 1):                # proj_drop
             ops.dropout_cast(dx, P[p + ".dyb_a"], M, C, self._ds(P, sp, 0), tok, **self._dkw(P, sp, 1))
-        self._wgrad(dh, Hd, P[p + ".xn2"], C, Hd, C, M, G(p + ".mlp.fc1.weight"), G(p + ".mlp.fc1.bias"))
+        wg("fc1")
         if sp.prefix in self.early_flush:
             # the last blocks of the backward: nothing is left to hide their weight gradients behind, so the MLP
             # half starts as soon as its operands exist instead of at the end of the block
@@ -1836,7 +1834,7 @@ class TulipEngine:
         dyb = P[p + ".dyb_a"]
         self._gemm(dyb, W_.p16(p + ".attn.proj.weight"), M, C, C, lda=C, ldb=C, b_trans=True, epi=EPI_BF16, out=dO,
                  ldo=C)
-        self._wgrad(dyb, C, P[p + ".o"], C, C, C, M, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"))
+        wg("proj")
         R = ops.window_attn_bwd_partial_rows(B, sp.H, sp.W, nh, sp.win)
         apart = P.scratch("apart." + p, R * nh * self.win_len ** 2)
         if drop and self._dp(sp, 0):
@@ -1849,10 +1847,8 @@ class TulipEngine:
         self._dgrad_ln_bwd(P, dqkv, W_.p16(p + ".attn.qkv.weight"), M, C, 3 * C, dxn,
                            (xin, P[p + ".mean1"], P[p + ".rstd1"], W_.p32(p + ".norm1.weight"), dx, dx, M, C,
                             G(p + ".norm1.weight"), G(p + ".norm1.bias"), p + ".1"), dict(cast=next_cast))
-        self._wgrad(dqkv, 3 * C, P[p + ".xn1"], C, 3 * C, C, M, G(p + ".attn.qkv.weight"), G(p + ".attn.qkv.bias"))
-        if self._lagged_hook is not None:
-            fn, self._lagged_hook = self._lagged_hook, None
-            fn()                                    # bucket join + all-reduce of the previous group, one block late
+        wg("qkv")
+        self._fire_lagged_hook()
 
     def _stage_bwd(self, P: Plan, specs: List[BlockSpec], stage_in, dx, G, have_dyb=False, next_cast=None):
         """have_dyb: the last block's dyb_m was already produced by whoever produced dx;

@@ -697,15 +697,26 @@ def kitti_range_map(points, n, rows, cols, ang_start_y, ang_res_y, ang_res_x, ma
                                             _stream()), "tulip_kitti_range_map")
 
 
+def _fill(cls, kw, numbers, default=None):
+    """cls() from keyword arguments named like its fields: tensors or addresses for the pointer fields (missing: NULL), plain values
+    for the fields in `numbers`.  default: what a missing number becomes -- None: nothing, the assignment raises (the geometry of a
+    Swin block descriptor must be given); 0 for the stage-boundary descriptors.  A keyword that is no field is a TypeError."""
+    d, kw = cls(), dict(kw)
+    for name, _t in cls._fields_:
+        v = kw.pop(name, None)
+        setattr(d, name, (default if v is None else v) if name in numbers else _p(v))
+    if kw:
+        raise TypeError(f"unknown fields {sorted(kw)}")
+    return d
+
+
+_SWIN_NUMBERS = ("B", "H", "W", "shift_h", "shift_w", "masked", "eps")      # of tulip_swin96_desc / tulip_swin96_bwd_desc
+
+
 def swin96_block_fwd(stamps=None, **kw):
     """tulip_swin96_block_fwd: keyword arguments are the fields of tulip_swin96_desc (tensors or addresses).
     stamps (int64 device tensor): the profiled twin."""
-    d = _lib.Swin96Desc()
-    for name, _t in _lib.Swin96Desc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked", "eps") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _swin96_desc(kw)
     if stamps is not None:
         check(_lib.load().tulip_swin96_block_fwd_profiled(ctypes.byref(d), _p(stamps), _stream()), "tulip_swin96_block_fwd_profiled")
         return
@@ -713,14 +724,7 @@ def swin96_block_fwd(stamps=None, **kw):
 
 
 def _swin96_desc(kw):
-    d = _lib.Swin96Desc()
-    kw = dict(kw)
-    for name, _t in _lib.Swin96Desc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked", "eps") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
-    return d
+    return _fill(_lib.Swin96Desc, kw, _SWIN_NUMBERS)
 
 
 def swin96_pair_sync_bytes(B, H, W) -> int:
@@ -743,12 +747,7 @@ def swinw_block_fwd(C, out_bf16=None, stamps=None, exchange=None, **kw):
     """tulip_swinw_block_fwd (C = 192 / 384): keyword arguments are the fields of tulip_swin96_desc.
     stamps (int64 device tensor): the profiled twin, per-wave shader-clock stamps at the phase boundaries.
     exchange (zeroed uint8 device tensor of swinw_split_bytes): tulip_swinw_block_fwd_split, two workgroups per window."""
-    d = _lib.Swin96Desc()
-    for name, _t in _lib.Swin96Desc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked", "eps") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _swin96_desc(kw)
     if exchange is not None:
         check(_lib.load().tulip_swinw_block_fwd_split(ctypes.byref(d), C, _p(out_bf16), _p(exchange),
                                                       exchange.numel() * exchange.element_size(), _p(stamps), _stream()),
@@ -778,12 +777,7 @@ def swinw_bwd_partial_rows(C, B, H, W) -> int:
 def swinw_block_bwd(C, exchange=None, **kw):
     """tulip_swinw_block_bwd: fields of tulip_swin96_bwd_desc; w_* are the TRANSPOSED bf16 weights.
     exchange: tulip_swinw_block_bwd_split (see swinw_block_fwd)."""
-    d = _lib.Swin96BwdDesc()
-    for name, _t in _lib.Swin96BwdDesc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _fill(_lib.Swin96BwdDesc, kw, _SWIN_NUMBERS)
     if exchange is not None:
         check(_lib.load().tulip_swinw_block_bwd_split(ctypes.byref(d), C, _p(exchange), exchange.numel() * exchange.element_size(),
                                                       _stream()), "tulip_swinw_block_bwd_split")
@@ -802,12 +796,7 @@ def swind_groups(C, B, H, W, win) -> int:
 
 def swind_block_fwd(C, win, out_bf16=None, phases=15, stamps=None, **kw):
     """tulip_swind_block_fwd (C = 768 / 1536): keyword arguments are the fields of tulip_swin96_desc; w_* fragment-major copies."""
-    d = _lib.Swin96Desc()
-    for name, _t in _lib.Swin96Desc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked", "eps") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _swin96_desc(kw)
     check(_lib.load().tulip_swind_block_fwd(ctypes.byref(d), C, int(win[0]), int(win[1]), _p(out_bf16), phases, _p(stamps),
                                             _stream()), "tulip_swind_block_fwd")
 
@@ -815,12 +804,7 @@ def swind_block_fwd(C, win, out_bf16=None, phases=15, stamps=None, **kw):
 def swind_block_bwd(C, win, d_norm_out, phases=15, stamps=None, **kw):
     """tulip_swind_block_bwd: fields of tulip_swin96_bwd_desc; w_* fragment-major copies of the TRANSPOSED weights; d_norm_out:
     fp32 [M][C] scratch that phases 2 / 8 fill for tulip_layernorm_bwd_splitk."""
-    d = _lib.Swin96BwdDesc()
-    for name, _t in _lib.Swin96BwdDesc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _fill(_lib.Swin96BwdDesc, kw, _SWIN_NUMBERS)
     check(_lib.load().tulip_swind_block_bwd(ctypes.byref(d), C, int(win[0]), int(win[1]), _p(d_norm_out), phases, _p(stamps),
                                             _stream()), "tulip_swind_block_bwd")
 
@@ -845,12 +829,7 @@ def swin96_bwd_partial_rows(B, H, W) -> int:
 
 def swin96_block_bwd(stamps=None, **kw):
     """tulip_swin96_block_bwd: keyword arguments are the fields of tulip_swin96_bwd_desc (tensors or addresses)."""
-    d = _lib.Swin96BwdDesc()
-    for name, _t in _lib.Swin96BwdDesc._fields_:
-        v = kw.pop(name, None)
-        setattr(d, name, _p(v) if name not in ("B", "H", "W", "shift_h", "shift_w", "masked") else v)
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
+    d = _fill(_lib.Swin96BwdDesc, kw, _SWIN_NUMBERS)
     if stamps is not None:
         check(_lib.load().tulip_swin96_block_bwd_profiled(ctypes.byref(d), _p(stamps), _stream()), "tulip_swin96_block_bwd_profiled")
         return
@@ -858,26 +837,13 @@ def swin96_block_bwd(stamps=None, **kw):
 
 
 # ---- the stage boundaries as one launch each (csrc/glue.hip): keyword arguments are the descriptor's fields
-def _fill(cls, kw, ints):
-    d = cls()
-    for name, _t in cls._fields_:
-        v = kw.pop(name, None)
-        if name in ints:
-            setattr(d, name, 0 if v is None else v)
-        else:
-            setattr(d, name, _p(v))
-    if kw:
-        raise TypeError(f"unknown fields {sorted(kw)}")
-    return d
-
-
 def merge_fwd_supported(Cin, B, H, W) -> bool:
     return bool(_lib.load().tulip_merge_fwd_supported(Cin, B, H, W))
 
 
 def merge_fwd(**kw):
     """tulip_merge_fwd: PatchMerging.forward (2x2 gather + LayerNorm + reduction GEMM) in one launch."""
-    d = _fill(_lib.MergeFwdDesc, kw, ("ld_bf16", "B", "H", "W", "Cin", "eps"))
+    d = _fill(_lib.MergeFwdDesc, kw, ("ld_bf16", "B", "H", "W", "Cin", "eps"), default=0)
     check(_lib.load().tulip_merge_fwd(ctypes.byref(d), _stream()), "tulip_merge_fwd")
 
 
@@ -891,7 +857,7 @@ def merge_bwd_partial_rows(Cp, B, H, W) -> int:
 
 def merge_bwd(**kw):
     """tulip_merge_bwd: [x_save half of the skip Linear's data gradient +] reduction data gradient + LayerNorm backward."""
-    d = _fill(_lib.MergeBwdDesc, kw, ("cast_rows_per_sample", "B", "H", "W", "Cp"))
+    d = _fill(_lib.MergeBwdDesc, kw, ("cast_rows_per_sample", "B", "H", "W", "Cp"), default=0)
     check(_lib.load().tulip_merge_bwd(ctypes.byref(d), _stream()), "tulip_merge_bwd")
 
 
@@ -901,11 +867,11 @@ def unmerge_skip_supported(C, B, H, W) -> bool:
 
 def unmerge_skip_fwd(**kw):
     """tulip_unmerge_skip_fwd: PatchUnmerging.forward -> skip Linear(cat[...]) in one launch."""
-    d = _fill(_lib.UnmergeSkipDesc, kw, ("B", "H", "W", "C"))
+    d = _fill(_lib.UnmergeSkipDesc, kw, ("B", "H", "W", "C"), default=0)
     check(_lib.load().tulip_unmerge_skip_fwd(ctypes.byref(d), _stream()), "tulip_unmerge_skip_fwd")
 
 
 def skip_unmerge_bwd(**kw):
     """tulip_skip_unmerge_bwd: the skip Linear's data gradient (unmerged half) -> PatchUnmerging's data gradient."""
-    d = _fill(_lib.SkipUnmergeBwdDesc, kw, ("cast_rows_per_sample", "B", "H", "W", "C"))
+    d = _fill(_lib.SkipUnmergeBwdDesc, kw, ("cast_rows_per_sample", "B", "H", "W", "C"), default=0)
     check(_lib.load().tulip_skip_unmerge_bwd(ctypes.byref(d), _stream()), "tulip_skip_unmerge_bwd")

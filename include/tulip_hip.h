@@ -566,6 +566,51 @@ int tulip_loss_edge_bwd_m(const float* pred, const float* target, const float* g
 int tulip_loss_edge_final_m(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H, int W,
                             const uint32_t* counts, hipStream_t stream);
 
+/* The channel weights, TULIP(loss_channel_weights=(w_0, .., w_{chans-1})) (host definition: tulip_amd/loss.py): the launches above
+ * with element e of channel c = (e / chan_stride) % chans COUNTED iff w_c > 0 and -- masked != 0 -- its pixel is valid
+ * (target[b, 0, pix] > valid_min, channel 0 even where w_0 == 0; masked == 0: valid_min is not read).  n_S, the number of counted
+ * elements, stands where n / n_v stand above: loss = (1 / n_S) sum_S w_c f(d), gradient g_c f'(d) with g = fl32(gscale / n_S) and
+ * g_c = fl32(w_c * g) once per channel, +0.0f at the elements that are not counted; BERHU: one C = 0.2f * max over S of |d|,
+ * unweighted; n_S == 0: zeros.  An element that is not counted enters nothing: a NaN or an infinity in a w_c == 0 channel of pred
+ * or target changes no bit.  `weights` is a HOST array of `chans` floats read during the call and passed to the kernels by value
+ * in the launch arguments: no device buffer holds them, and a captured graph keeps the values it was captured with.  One family
+ * for the masked and the unmasked case; counts / n_valid as in the _m forms, always.
+ *   tulip_loss_stats_w  stats[4 wg + {0, 1, 2, 3}] = {sum w_c |d|, the UNWEIGHTED metric sum -- |expm1(pred) - expm1(target)| with
+ *                       log_transform, |d| without --, sum w_c d^2, max |d|} over the workgroup's counted elements (value terms
+ *                       fl32(w_c * term), then the sums above; d^2 as fl32(w_c * d) * d into the accumulator), counts[wg] = how
+ *                       many there were.  The weighted L1 value and the metric are different sums: slot 1 is always filled
+ *   tulip_loss_bwd_w    as tulip_loss_bwd_m with g_c where g stands; n_valid[0] = n_S
+ *   tulip_loss_value_w  BERHU's second pass: the sums of fl32(w_c * value) over the counted elements
+ *   tulip_loss_final_w  losses[0] = the weighted loss of `kind`, losses[1] = slot 1's sum / n_S (the L1 metric over S); n_valid[0] = n_S
+ *   tulip_loss_edge_stats_w  the sums of fl32(w_c * fl32(|e_h| + |e_v|)), c = plane % chans; a plane with w_c == 0 is not read
+ *   tulip_loss_edge_bwd_w    ge_c = fl32(weight * g_c) where ge stands, n_S from `counts` (masked or not); a plane with w_c == 0
+ *                            is neither read nor written: dpred keeps the +0.0f tulip_loss_bwd_w wrote there
+ *   tulip_loss_edge_final_w  tulip_loss_edge_final_m's fold with n_S
+ * Same grids as above; every thread takes the elements the unweighted kernel of the same case gives it (groups of four where the
+ * pointers are 16-byte aligned -- masked: and chan_stride % 4 == 0 --, a scalar tail), so with every w_c == 1.0f the results are
+ * that kernel's, bit for bit.  A group is loaded as a float4 only where chan_stride % 4 == 0 (it then lies in one channel);
+ * elsewhere by four scalar loads, every element with its own channel.  Fixed reduction orders, plain stores, no atomics, 64-bit
+ * element offsets, graph-capturable.
+ * TULIP_ERR_ARG before any launch, besides the cases of the _m forms: chans outside 1..4, a NULL weights, a negative, NaN or
+ * infinite weight, all weights 0. */
+int tulip_loss_stats_w(const float* pred, const float* target, float* stats, int64_t n, int log_transform, int chans,
+                       int64_t chan_stride, const float* weights, int masked, float valid_min, uint32_t* counts, hipStream_t stream);
+int tulip_loss_bwd_w(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev, float gscale,
+                     float* dpred, float* loss_c, int64_t n, int chans, int64_t chan_stride, const float* weights, int masked,
+                     float valid_min, const uint32_t* counts, int64_t* n_valid, hipStream_t stream);
+int tulip_loss_value_w(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n, int chans,
+                       int64_t chan_stride, const float* weights, int masked, float valid_min, const uint32_t* counts,
+                       hipStream_t stream);
+int tulip_loss_final_w(int kind, const float* stats, const float* value_partials, float* losses, int64_t n, const uint32_t* counts,
+                       int64_t* n_valid, hipStream_t stream);
+int tulip_loss_edge_stats_w(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W, int chans,
+                            const float* weights, int masked, float valid_min, hipStream_t stream);
+int tulip_loss_edge_bwd_w(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight,
+                          float* dpred, int64_t planes, int H, int W, int chans, const float* weights, int masked,
+                          float valid_min, const uint32_t* counts, hipStream_t stream);
+int tulip_loss_edge_final_w(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes, int H, int W,
+                            const uint32_t* counts, hipStream_t stream);
+
 /* Fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, main_lidar_upsampling.py:283):
  * hyper (device, 8 floats) = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}.
  * decay_mask64[i/64] bit 0 selects weight decay for elements of 64-float block i/64 (timm's grouping,

@@ -195,6 +195,14 @@ SIGNATURES = {
     "tulip_loss_edge_stats_m": [P, P, P, L, I, I, I, F, P],
     "tulip_loss_edge_bwd_m": [P, P, P, F, F, P, L, I, I, I, F, P, P],
     "tulip_loss_edge_final_m": [P, P, P, F, L, I, I, P, P],
+    # the channel weights (TULIP(loss_channel_weights=...)): + chans, chan_stride, weights (a host array), masked, valid_min, counts
+    "tulip_loss_stats_w": [P, P, P, L, I, I, L, P, I, F, P, P],
+    "tulip_loss_bwd_w": [I, P, P, P, P, F, P, P, L, I, L, P, I, F, P, P, P],
+    "tulip_loss_value_w": [P, P, P, P, L, I, L, P, I, F, P, P],
+    "tulip_loss_final_w": [I, P, P, P, L, P, P, P],
+    "tulip_loss_edge_stats_w": [P, P, P, L, I, I, I, P, I, F, P],
+    "tulip_loss_edge_bwd_w": [P, P, P, F, F, P, L, I, I, I, P, I, F, P, P],
+    "tulip_loss_edge_final_w": [P, P, P, F, L, I, I, P, P],
     "tulip_adamw": [P, P, P, P, P, L, P, P, I, P],
     "tulip_adamw_blocks": [P, P, P, P, P, P, I, P, P, I, P],
     # ... and with a trailing-but-one lr_scale64 table: per-group learning-rate scales (group = mask byte >> 2)

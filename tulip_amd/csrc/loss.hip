@@ -392,6 +392,14 @@ struct EdgeMask {
     float valid_min;
 };
 
+// The channel weights of the _w entry points (TULIP(loss_channel_weights=...)), by value in the launch arguments: w[c] of channel
+// c < chans, 0 behind them.  Nothing on the device holds them, so nothing can rewrite them under a captured graph.
+struct ChanW {
+    float w0, w1, w2, w3;
+};
+// (a select chain, not an index: the argument stays in scalar registers)
+__device__ __forceinline__ float chan_weight(int c, const ChanW& w) { return c == 0 ? w.w0 : c == 1 ? w.w1 : c == 2 ? w.w2 : w.w3; }
+
 struct EdgeGeom {
     int H, W, tiles_x, tiles_y;
     int64_t tiles;             // planes * tiles_y * tiles_x
@@ -456,10 +464,11 @@ __device__ __forceinline__ void edge_tile(int64_t t, const EdgeGeom& g, int64_t&
 }
 
 // edge_partials[wg] = the workgroup's sum of |e_h| + |e_v| over its tiles (MASK: over the responses centred on a valid pixel):
-// per thread over its tiles and rows in order, the wave tree, four wave results
-template <bool MASK>
+// per thread over its tiles and rows in order, the wave tree, four wave results.  WT: the terms fl32(w_c * fl32(|e_h| + |e_v|)), c
+// the plane's channel (plane % k.chans); a plane with w_c == 0 is skipped -- nothing of it is read
+template <bool MASK, bool WT>
 __global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                         float* __restrict__ edge_partials, EdgeGeom g, EdgeMask k) {
+                                                         float* __restrict__ edge_partials, EdgeGeom g, EdgeMask k, ChanW cw) {
     constexpr int PW = EDGE_TW + 2;
     __shared__ float sd[(EDGE_TH + 2) * PW];
     __shared__ uint8_t ok[(EDGE_TH + 2) * PW];
@@ -470,6 +479,11 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict
         int64_t plane;
         int y0, x0;
         edge_tile(t, g, plane, y0, x0);
+        float w = 1.f;
+        if constexpr (WT) {
+            w = chan_weight((int)(plane % k.chans), cw);
+            if (!(w > 0.f)) continue;                  // (the same plane in every thread: a uniform skip)
+        }
         edge_stage<1, MASK>(sd, ok, pred, tgt, plane, y0, x0, g, k);
         __syncthreads();
 #pragma unroll
@@ -478,7 +492,8 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict
             if (ok[c]) {                               // inside the plane (and valid)
                 float eh, ev;
                 edge_responses<PW>(sd, c, eh, ev);
-                s += fabsf(eh) + fabsf(ev);
+                if constexpr (WT) s = mul_then_add(w, fabsf(eh) + fabsf(ev), s);
+                else s += fabsf(eh) + fabsf(ev);
             }
         }
         __syncthreads();
@@ -491,31 +506,38 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict
 // dpred[e] = fl32(dpred[e] + fl32(ge * k[e])), ge = fl32(weight * g) with g the base gradient's fl32(gscale / n) (MASK: n_v folded
 // here from the counts; g = 0 when n_v == 0), k the adjoint taps over the two sign maps -- signs zeroed where their centre is
 // outside the plane (MASK: or invalid); a NaN response has sign 0.  MASK: +0 at the invalid elements.  Every thread reads and
-// writes its own elements of dpred only.
-template <bool MASK>
+// writes its own elements of dpred only.  WT: n_S from the counts (masked or not), ge_c = fl32(weight * fl32(w_c * g)) per plane,
+// and a plane with w_c == 0 is skipped: nothing of it is read, and dpred keeps the +0 the base gradient's launch wrote there.
+template <bool MASK, bool WT>
 __global__ __launch_bounds__(256) void edge_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                        const float* __restrict__ gscale_dev, float gscale, float weight,
                                                        float* __restrict__ dpred, int64_t n, const uint32_t* __restrict__ counts,
-                                                       int nb_counts, EdgeGeom g, EdgeMask k) {
+                                                       int nb_counts, EdgeGeom g, EdgeMask k, ChanW cw) {
     constexpr int PW2 = EDGE_TW + 4, PW1 = EDGE_TW + 2, N1 = (EDGE_TH + 2) * PW1;
     __shared__ float sd[(EDGE_TH + 4) * PW2];
     __shared__ uint8_t ok[(EDGE_TH + 4) * PW2];
     __shared__ int8_t sh[N1], sv[N1];
     float gg;
-    if constexpr (MASK) {
+    if constexpr (MASK || WT) {
         __shared__ long long cred[4];
         const int64_t nv = valid_count(counts, nb_counts, cred);
         gg = nv ? (gscale_dev ? gscale_dev[0] : gscale) / (float)nv : 0.f;
     } else {
         gg = (gscale_dev ? gscale_dev[0] : gscale) / (float)n;
     }
-    const float ge = weight * gg;
+    float ge = weight * gg;
     const int col = threadIdx.x & (EDGE_TW - 1), row0 = (threadIdx.x >> 7) * 4;
     const int64_t hw = (int64_t)g.H * g.W;
     for (int64_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
         int64_t plane;
         int y0, x0;
         edge_tile(t, g, plane, y0, x0);
+        if constexpr (WT) {
+            const float w = chan_weight((int)(plane % k.chans), cw);
+            if (!(w > 0.f)) continue;                  // (uniform)
+            const float gc = w * gg;
+            ge = weight * gc;
+        }
         edge_stage<2, MASK>(sd, ok, pred, tgt, plane, y0, x0, g, k);
         __syncthreads();
         for (int i = threadIdx.x; i < N1; i += 256) {
@@ -599,29 +621,38 @@ inline bool make_edge_mask(EdgeMask& k, int64_t planes, int chans, float valid_m
 
 inline int edge_grid(const EdgeGeom& g) { return (int)(g.tiles > LOSS_BLOCKS ? LOSS_BLOCKS : g.tiles); }
 
+// cw: the weighted kernels (k then carries the channel count whether `masked` or not)
 int launch_edge_stats(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
-                      const EdgeMask* k, hipStream_t stream) {
+                      const EdgeMask* k, hipStream_t stream, const ChanW* cw = nullptr, bool masked = true) {
     EdgeGeom g;
     int64_t n;
     if (!make_edge(g, n, planes, H, W) || !pred || !target || !edge_partials || ((uintptr_t)edge_partials & 3)) return TULIP_ERR_ARG;
     const dim3 grid(edge_grid(g)), block(256);
-    if (k) hipLaunchKernelGGL(edge_stats_kernel<true>, grid, block, 0, stream, pred, target, edge_partials, g, *k);
-    else hipLaunchKernelGGL(edge_stats_kernel<false>, grid, block, 0, stream, pred, target, edge_partials, g, EdgeMask{1, 0.f});
+    if (cw && masked) hipLaunchKernelGGL((edge_stats_kernel<true, true>), grid, block, 0, stream, pred, target, edge_partials, g, *k, *cw);
+    else if (cw) hipLaunchKernelGGL((edge_stats_kernel<false, true>), grid, block, 0, stream, pred, target, edge_partials, g, *k, *cw);
+    else if (k) hipLaunchKernelGGL((edge_stats_kernel<true, false>), grid, block, 0, stream, pred, target, edge_partials, g, *k, ChanW{});
+    else hipLaunchKernelGGL((edge_stats_kernel<false, false>), grid, block, 0, stream, pred, target, edge_partials, g, EdgeMask{1, 0.f},
+                            ChanW{});
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
 
 int launch_edge_bwd(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight, float* dpred,
-                    int64_t planes, int H, int W, const EdgeMask* k, const uint32_t* counts, hipStream_t stream) {
+                    int64_t planes, int H, int W, const EdgeMask* k, const uint32_t* counts, hipStream_t stream,
+                    const ChanW* cw = nullptr, bool masked = true) {
     EdgeGeom g;
     int64_t n;
     if (!make_edge(g, n, planes, H, W) || !pred || !target || !dpred || bad_weight(weight)) return TULIP_ERR_ARG;
     if (k && (!counts || ((uintptr_t)counts & 3))) return TULIP_ERR_ARG;
     const dim3 grid(edge_grid(g)), block(256);
-    if (k) hipLaunchKernelGGL(edge_bwd_kernel<true>, grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred, n, counts,
-                              tulip_loss_blocks(n), g, *k);
-    else hipLaunchKernelGGL(edge_bwd_kernel<false>, grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred, n,
-                            (const uint32_t*)nullptr, 0, g, EdgeMask{1, 0.f});
+    if (cw && masked) hipLaunchKernelGGL((edge_bwd_kernel<true, true>), grid, block, 0, stream, pred, target, gscale_dev, gscale, weight,
+                                         dpred, n, counts, tulip_loss_blocks(n), g, *k, *cw);
+    else if (cw) hipLaunchKernelGGL((edge_bwd_kernel<false, true>), grid, block, 0, stream, pred, target, gscale_dev, gscale, weight,
+                                    dpred, n, counts, tulip_loss_blocks(n), g, *k, *cw);
+    else if (k) hipLaunchKernelGGL((edge_bwd_kernel<true, false>), grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred,
+                                   n, counts, tulip_loss_blocks(n), g, *k, ChanW{});
+    else hipLaunchKernelGGL((edge_bwd_kernel<false, false>), grid, block, 0, stream, pred, target, gscale_dev, gscale, weight, dpred, n,
+                            (const uint32_t*)nullptr, 0, g, EdgeMask{1, 0.f}, ChanW{});
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
@@ -637,6 +668,244 @@ int launch_edge_final(const float* edge_partials, float* edge_out, float* losses
                                    weight, 0.0, counts, tulip_loss_blocks(n));
     else hipLaunchKernelGGL(edge_final_kernel<false>, dim3(1), dim3(256), 0, stream, edge_partials, edge_grid(g), edge_out, losses,
                             weight, 1.0 / (double)n, (const uint32_t*)nullptr, 0);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+// ---- the channel weights, TULIP(loss_channel_weights=(w_0, ..)) (tulip_amd/loss.py): the flat kernels again with element e of
+// channel c = (e / chan_stride) % chans COUNTED iff w_c > 0 and (masked) its pixel is valid.  One family for the unmasked and the
+// masked case (`masked` at run time); the counted elements are always counted in integers (k.m.counts), and n_S, their sum, stands
+// where n / n_v stand above.  stats[4 wg + {0, 1, 2, 3}] = {sum w_c |d|, the UNWEIGHTED metric sum (|expm1 p - expm1 t| with
+// log_transform, |d| without), sum w_c d^2, max |d|} over the counted elements: the weighted L1 value and the metric are different
+// sums now, so the second slot is always filled and the final fold (loss_final_kernel<LossMask>) always reads it.
+// Threads take the elements the kernels above give them -- groups of four where the pointers are 16-byte aligned (masked: and
+// chan_stride % 4 == 0), a scalar tail -- so that the reduction orders, and with all weights 1 every bit, are theirs.  A group is
+// loaded as a float4 only where it lies in one channel (vec: chan_stride % 4 == 0); elsewhere by four scalar loads, each element
+// with its own channel.
+struct LossW {
+    LossMask m;
+    ChanW w;
+    int masked;
+    int vec;
+};
+
+__device__ __forceinline__ float weight_at(int64_t e, const LossW& k) {
+    int c;
+    if (k.m.narrow) c = (int)(((uint32_t)e / (uint32_t)k.m.chan_stride) % (uint32_t)k.m.chans);
+    else c = (int)((e / k.m.chan_stride) % k.m.chans);
+    return chan_weight(c, k.w);
+}
+__device__ __forceinline__ float4 weights4(int64_t e, const LossW& k) {
+    if (k.vec) {
+        const float w = weight_at(e, k);
+        return make_float4(w, w, w, w);
+    }
+    return make_float4(weight_at(e, k), weight_at(e + 1, k), weight_at(e + 2, k), weight_at(e + 3, k));
+}
+__device__ __forceinline__ float4 load4(const float* __restrict__ a, int64_t e, const LossW& k) {
+    if (k.vec) return *(const float4*)(a + e);
+    return make_float4(a[e], a[e + 1], a[e + 2], a[e + 3]);
+}
+// counted: w > 0 and, masked, the pixel valid (a masked group is always a float4 group: vec_groups_m)
+struct Counted {
+    bool x, y, z, w;
+};
+__device__ __forceinline__ Counted counted4(const float* __restrict__ tgt, int64_t e, float4 t, float4 w, const LossW& k) {
+    Counted c{w.x > 0.f, w.y > 0.f, w.z > 0.f, w.w > 0.f};
+    if (k.masked) {
+        const float4 z = mask_src4(tgt, e, t, k.m);
+        c = Counted{c.x && z.x > k.m.valid_min, c.y && z.y > k.m.valid_min, c.z && z.z > k.m.valid_min, c.w && z.w > k.m.valid_min};
+    }
+    return c;
+}
+__device__ __forceinline__ bool counted1(const float* __restrict__ tgt, int64_t e, float t, float w, const LossW& k) {
+    return w > 0.f && (!k.masked || mask_src(tgt, e, t, k.m) > k.m.valid_min);
+}
+
+struct LossAccW {
+    float abs = 0.f, pix = 0.f, sq = 0.f, mx = 0.f;
+    uint32_t cnt = 0;
+    // an element that is not counted enters nothing, whatever p and t hold there
+    __device__ __forceinline__ void add_if(bool counted, float w, float p, float t, int log_transform) {
+        if (counted) {
+            const float d = p - t, a = fabsf(d);
+            abs = mul_then_add(w, a, abs);
+            pix += log_transform ? fabsf(expm1f(p) - expm1f(t)) : a;
+            sq += (w * d) * d;
+            mx = nan_max(mx, a);
+            ++cnt;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void loss_stats_w_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                           float* __restrict__ stats, int64_t n, int64_t n4, int log_transform,
+                                                           LossW k) {
+    __shared__ float red[4][4];
+    __shared__ uint32_t cred[4];
+    LossAccW s;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = first; i < n4; i += stride) {
+        const float4 p = load4(pred, i * 4, k), t = load4(tgt, i * 4, k), w = weights4(i * 4, k);
+        const Counted c = counted4(tgt, i * 4, t, w, k);
+        s.add_if(c.x, w.x, p.x, t.x, log_transform); s.add_if(c.y, w.y, p.y, t.y, log_transform);
+        s.add_if(c.z, w.z, p.z, t.z, log_transform); s.add_if(c.w, w.w, p.w, t.w, log_transform);
+    }
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        const float w = weight_at(i, k), t = tgt[i];
+        s.add_if(counted1(tgt, i, t, w, k), w, pred[i], t, log_transform);
+    }
+    uint32_t c = s.cnt;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) k.m.counts[blockIdx.x] = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+    block_sum(s.abs, red, 0);
+    block_sum(s.pix, red, 1);
+    block_sum(s.sq, red, 2);
+    const float m = group_reduce<64>(s.mx, [](float a, float b) { return nan_max(a, b); });
+    if ((threadIdx.x & 63) == 0) red[3][threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *(float4*)(stats + 4 * (size_t)blockIdx.x) =
+            make_float4((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]),
+                        (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]),
+                        nan_max(nan_max(red[3][0], red[3][1]), nan_max(red[3][2], red[3][3])));
+    }
+}
+
+// dpred[i] = grad_kind(d_i; C) with g_c = fl32(w_c * g) where g stands above, g = fl32(gscale / n_S) (0 when n_S == 0); +0 at the
+// elements that are not counted.  n_S is written to k.m.n_valid
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_bwd_w_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                         const float* __restrict__ stats, int nb,
+                                                         const float* __restrict__ gscale_dev, float gscale,
+                                                         float* __restrict__ dpred, float* __restrict__ loss_c, int64_t n,
+                                                         int64_t n4, LossW k) {
+    __shared__ float red[4];
+    __shared__ long long cred[4];
+    float C = 0.f;
+    if constexpr (KIND == TULIP_LOSS_BERHU) {
+        C = berhu_threshold(stats, nb, red);
+        if (blockIdx.x == 0 && threadIdx.x == 0) loss_c[0] = C;
+    }
+    const int64_t nv = valid_count(k.m.counts, nb, cred);
+    if (blockIdx.x == 0 && threadIdx.x == 0) k.m.n_valid[0] = nv;
+    const float g = nv ? (gscale_dev ? gscale_dev[0] : gscale) / (float)nv : 0.f;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = first; i < n4; i += stride) {
+        const float4 p = load4(pred, i * 4, k), t = load4(tgt, i * 4, k), w = weights4(i * 4, k);
+        const Counted c = counted4(tgt, i * 4, t, w, k);
+        const float4 d = make_float4(c.x ? loss_grad<KIND>(p.x, t.x, C, w.x * g) : 0.f, c.y ? loss_grad<KIND>(p.y, t.y, C, w.y * g) : 0.f,
+                                     c.z ? loss_grad<KIND>(p.z, t.z, C, w.z * g) : 0.f, c.w ? loss_grad<KIND>(p.w, t.w, C, w.w * g) : 0.f);
+        if (k.vec) {
+            *(float4*)(dpred + i * 4) = d;
+        } else {
+            dpred[i * 4] = d.x; dpred[i * 4 + 1] = d.y; dpred[i * 4 + 2] = d.z; dpred[i * 4 + 3] = d.w;
+        }
+    }
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        const float w = weight_at(i, k), t = tgt[i];
+        dpred[i] = counted1(tgt, i, t, w, k) ? loss_grad<KIND>(pred[i], t, C, w * g) : 0.f;
+    }
+}
+
+// berHu's second pass: vpart[wg] = the workgroup's sum of fl32(w_c * value) over the counted elements (n_S == 0: nothing is read)
+__global__ __launch_bounds__(256) void loss_value_w_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                           const float* __restrict__ stats, int nb, float* __restrict__ vpart,
+                                                           int64_t n, int64_t n4, LossW k) {
+    __shared__ float red[4];
+    __shared__ float sum[1][4];
+    __shared__ long long cred[4];
+    if (valid_count(k.m.counts, nb, cred) == 0) {          // (the same n_S in every thread: a uniform exit)
+        if (threadIdx.x == 0) vpart[blockIdx.x] = 0.f;
+        return;
+    }
+    const float C = berhu_threshold(stats, nb, red);
+    float s = 0.f;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = first; i < n4; i += stride) {
+        const float4 p = load4(pred, i * 4, k), t = load4(tgt, i * 4, k), w = weights4(i * 4, k);
+        const Counted c = counted4(tgt, i * 4, t, w, k);
+        if (c.x) s = mul_then_add(w.x, berhu_value(p.x - t.x, C), s);
+        if (c.y) s = mul_then_add(w.y, berhu_value(p.y - t.y, C), s);
+        if (c.z) s = mul_then_add(w.z, berhu_value(p.z - t.z, C), s);
+        if (c.w) s = mul_then_add(w.w, berhu_value(p.w - t.w, C), s);
+    }
+    for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+        const float w = weight_at(i, k), t = tgt[i];
+        if (counted1(tgt, i, t, w, k)) s = mul_then_add(w, berhu_value(pred[i] - t, C), s);
+    }
+    block_sum(s, sum, 0);
+    __syncthreads();
+    if (threadIdx.x == 0) vpart[blockIdx.x] = (sum[0][0] + sum[0][1]) + (sum[0][2] + sum[0][3]);
+}
+
+// the weights of a _w call, checked: false for what TULIP_ERR_ARG refuses
+inline bool make_chan_w(ChanW& cw, const float* weights, int chans) {
+    if (chans < 1 || chans > 4 || !weights) return false;
+    float w[4] = {0.f, 0.f, 0.f, 0.f};
+    bool any = false;
+    for (int c = 0; c < chans; ++c) {
+        if (bad_weight(weights[c])) return false;
+        w[c] = weights[c];
+        any = any || w[c] > 0.f;
+    }
+    if (!any) return false;
+    cw = ChanW{w[0], w[1], w[2], w[3]};
+    return true;
+}
+
+inline bool make_loss_w(LossW& k, int64_t n, int chans, int64_t chan_stride, const float* weights, int masked, float valid_min,
+                        const uint32_t* counts, int64_t* n_valid, bool wants_n_valid) {
+    ChanW cw;
+    if (!make_chan_w(cw, weights, chans)) return false;
+    LossMask m;
+    if (!make_mask(m, n, chans, chan_stride, masked ? valid_min : 0.f, counts, n_valid, wants_n_valid)) return false;
+    k = LossW{m, cw, masked != 0, (chan_stride & 3) == 0};
+    return true;
+}
+
+// the groups of the kernels above for the same pointers: masked the _m rule, unmasked the alignment alone
+inline int64_t groups_w(const LossW& k, int64_t n, const void* a, const void* b, const void* c = nullptr) {
+    return k.masked ? vec_groups_m(&k.m, n, a, b, c) : vec_groups(n, a, b, c);
+}
+
+int launch_stats_w(const float* pred, const float* target, float* stats, int64_t n, int log_transform, const LossW& k,
+                   hipStream_t stream) {
+    if (n <= 0 || !pred || !target || !stats || ((uintptr_t)stats & 15)) return TULIP_ERR_ARG;
+    hipLaunchKernelGGL(loss_stats_w_kernel, dim3(tulip_loss_blocks(n)), dim3(256), 0, stream, pred, target, stats, n,
+                       groups_w(k, n, pred, target), log_transform, k);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_bwd_w(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev, float gscale,
+                 float* dpred, float* loss_c, int64_t n, const LossW& k, hipStream_t stream) {
+    if (bad_kind(kind) || n <= 0 || !pred || !target || !dpred) return TULIP_ERR_ARG;
+    if (kind == TULIP_LOSS_BERHU && (!stats || !loss_c)) return TULIP_ERR_ARG;
+    const int nb = tulip_loss_blocks(n);
+    const int64_t n4 = groups_w(k, n, pred, target, dpred);
+    const dim3 grid(nb), block(256);
+    if (kind == TULIP_LOSS_L1)
+        hipLaunchKernelGGL(loss_bwd_w_kernel<TULIP_LOSS_L1>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale, dpred,
+                           loss_c, n, n4, k);
+    else if (kind == TULIP_LOSS_L2)
+        hipLaunchKernelGGL(loss_bwd_w_kernel<TULIP_LOSS_L2>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale, dpred,
+                           loss_c, n, n4, k);
+    else
+        hipLaunchKernelGGL(loss_bwd_w_kernel<TULIP_LOSS_BERHU>, grid, block, 0, stream, pred, target, stats, nb, gscale_dev, gscale,
+                           dpred, loss_c, n, n4, k);
+    TULIP_CHECK_LAUNCH();
+    return TULIP_OK;
+}
+
+int launch_value_w(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n, const LossW& k,
+                   hipStream_t stream) {
+    if (n <= 0 || !pred || !target || !stats || !value_partials) return TULIP_ERR_ARG;
+    const int nb = tulip_loss_blocks(n);
+    hipLaunchKernelGGL(loss_value_w_kernel, dim3(nb), dim3(256), 0, stream, pred, target, stats, nb, value_partials, n,
+                       groups_w(k, n, pred, target), k);
     TULIP_CHECK_LAUNCH();
     return TULIP_OK;
 }
@@ -737,6 +1006,67 @@ extern "C" int tulip_loss_edge_bwd_m(const float* pred, const float* target, con
 }
 
 extern "C" int tulip_loss_edge_final_m(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes,
+                                       int H, int W, const uint32_t* counts, hipStream_t stream) {
+    return launch_edge_final(edge_partials, edge_out, losses, weight, planes, H, W, true, counts, stream);
+}
+
+// ---- the weighted entry points (TULIP(loss_channel_weights=...)): `weights` is a HOST array of `chans` floats, copied into the
+// launch arguments here
+extern "C" int tulip_loss_stats_w(const float* pred, const float* target, float* stats, int64_t n, int log_transform, int chans,
+                                  int64_t chan_stride, const float* weights, int masked, float valid_min, uint32_t* counts,
+                                  hipStream_t stream) {
+    LossW k;
+    if (!make_loss_w(k, n, chans, chan_stride, weights, masked, valid_min, counts, nullptr, false)) return TULIP_ERR_ARG;
+    return launch_stats_w(pred, target, stats, n, log_transform, k, stream);
+}
+
+extern "C" int tulip_loss_bwd_w(int kind, const float* pred, const float* target, const float* stats, const float* gscale_dev,
+                                float gscale, float* dpred, float* loss_c, int64_t n, int chans, int64_t chan_stride,
+                                const float* weights, int masked, float valid_min, const uint32_t* counts, int64_t* n_valid,
+                                hipStream_t stream) {
+    LossW k;
+    if (!make_loss_w(k, n, chans, chan_stride, weights, masked, valid_min, counts, n_valid, true)) return TULIP_ERR_ARG;
+    return launch_bwd_w(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n, k, stream);
+}
+
+extern "C" int tulip_loss_value_w(const float* pred, const float* target, const float* stats, float* value_partials, int64_t n,
+                                  int chans, int64_t chan_stride, const float* weights, int masked, float valid_min,
+                                  const uint32_t* counts, hipStream_t stream) {
+    LossW k;
+    if (!make_loss_w(k, n, chans, chan_stride, weights, masked, valid_min, counts, nullptr, false)) return TULIP_ERR_ARG;
+    return launch_value_w(pred, target, stats, value_partials, n, k, stream);
+}
+
+// (stats' second slot is the metric sum whatever log_transform was: the masked fold, reading that slot)
+extern "C" int tulip_loss_final_w(int kind, const float* stats, const float* value_partials, float* losses, int64_t n,
+                                  const uint32_t* counts, int64_t* n_valid, hipStream_t stream) {
+    LossMask k;
+    if (!make_mask(k, n, 1, 1, 0.f, counts, n_valid, true)) return TULIP_ERR_ARG;
+    return launch_final(kind, stats, value_partials, losses, n, 1, &k, stream);
+}
+
+inline bool make_edge_w(EdgeMask& k, ChanW& cw, int64_t planes, int chans, const float* weights, int masked, float valid_min) {
+    return make_chan_w(cw, weights, chans) && make_edge_mask(k, planes, chans, masked ? valid_min : 0.f);
+}
+
+extern "C" int tulip_loss_edge_stats_w(const float* pred, const float* target, float* edge_partials, int64_t planes, int H, int W,
+                                       int chans, const float* weights, int masked, float valid_min, hipStream_t stream) {
+    EdgeMask k;
+    ChanW cw;
+    if (!make_edge_w(k, cw, planes, chans, weights, masked, valid_min)) return TULIP_ERR_ARG;
+    return launch_edge_stats(pred, target, edge_partials, planes, H, W, &k, stream, &cw, masked != 0);
+}
+
+extern "C" int tulip_loss_edge_bwd_w(const float* pred, const float* target, const float* gscale_dev, float gscale, float weight,
+                                     float* dpred, int64_t planes, int H, int W, int chans, const float* weights, int masked,
+                                     float valid_min, const uint32_t* counts, hipStream_t stream) {
+    EdgeMask k;
+    ChanW cw;
+    if (!make_edge_w(k, cw, planes, chans, weights, masked, valid_min)) return TULIP_ERR_ARG;
+    return launch_edge_bwd(pred, target, gscale_dev, gscale, weight, dpred, planes, H, W, &k, counts, stream, &cw, masked != 0);
+}
+
+extern "C" int tulip_loss_edge_final_w(const float* edge_partials, float* edge_out, float* losses, float weight, int64_t planes,
                                        int H, int W, const uint32_t* counts, hipStream_t stream) {
     return launch_edge_final(edge_partials, edge_out, losses, weight, planes, H, W, true, counts, stream);
 }

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib, knobs, ops
-from .loss import check_edge_weight, check_loss, check_valid_min
+from .loss import check_channel_weights, check_edge_weight, check_loss, check_valid_min
 from ._lib import (EPI_BF16, EPI_F32, EPI_GELU_BWD, EPI_GELU_DUAL, EPI_PIXSHUF2_F32, EPI_RESID_F32,
                    EPI_UNSHUF2_BF16,
                    EPI_SPLIT_F32)
@@ -313,15 +313,17 @@ class Plan:
         self.partials = self.f32("partials", max(2048, 2 * ((B * H0 * W0 + 31) // 32)))   # loss partial sums (2 per block)
         self.gscale = self.f32("gscale", 1)
         self.gscale.fill_(1.0)
-        if eng.loss_kind != "l1" or eng.loss_valid_min is not None:
+        weighted = eng.loss_channel_weights is not None   # TULIP(loss_channel_weights=...): the buffers of the masked loss, always
+        if eng.loss_kind != "l1" or eng.loss_valid_min is not None or weighted:
             # TULIP(loss="l2" | "berhu") (tulip_amd/loss.py): the per-workgroup partials of tulip_loss_stats / tulip_loss_value and
             # berHu's threshold C = 0.2 max|pred - target| as the backward formed it (a device float, never read back by the step)
             self.loss_stats = self.f32("loss_stats", 4 * _lib.LOSS_BLOCKS_MAX).zero_()
             self.loss_vpart = self.f32("loss_vpart", _lib.LOSS_BLOCKS_MAX).zero_()
             self.loss_c = self.f32("loss_c", 1).zero_()
-        if eng.loss_valid_min is not None:
+        if eng.loss_valid_min is not None or weighted:
             # TULIP(loss_valid_min=...), masked "l1" included: the valid elements tulip_loss_stats_m counted per workgroup (uint32
-            # on the device) and their sum n_v as the backward / the final fold formed it (a device int64, never read back)
+            # on the device) and their sum n_v as the backward / the final fold formed it (a device int64, never read back);
+            # with channel weights the counted elements of tulip_loss_stats_w and their sum n_S
             self.loss_counts = self._alloc("loss_counts", (_lib.LOSS_BLOCKS_MAX,), torch.int32, dev).zero_()
             self.loss_valid = self._alloc("loss_valid", (1,), torch.int64, dev).zero_()
         if eng.loss_edge_weight > 0.0:
@@ -1069,6 +1071,18 @@ class TulipEngine:
         object without the attribute."""
         return check_edge_weight(getattr(self.model, "loss_edge_weight", 0.0))
 
+    @property
+    def loss_channel_weights(self) -> Optional[tuple]:
+        """The model's channel weights (TULIP(loss_channel_weights=...), tulip_amd/loss.py); None -- no weights -- for a model
+        object without the attribute."""
+        w = getattr(self.model, "loss_channel_weights", None)
+        return None if w is None else check_channel_weights(tuple(w), self.model.in_chans)
+
+    def _loss_w(self, P: Plan) -> tuple:
+        """(chans, chan_stride, weights, valid_min) of the weighted launches on P.pred / P.target (B, in_chans, H, W); the weights
+        travel by value in every launch's arguments"""
+        return P.target.shape[1], P.target.shape[2] * P.target.shape[3], self.loss_channel_weights, self.loss_valid_min
+
     def _loss_mask(self, P: Plan) -> tuple:
         """(chans, chan_stride, valid_min) of the masked launches on P.pred / P.target (B, in_chans, H, W)"""
         return P.target.shape[1], P.target.shape[2] * P.target.shape[3], self.loss_valid_min
@@ -1090,6 +1104,11 @@ class TulipEngine:
         def both():
             fin()
             dims, kw = self._edge_args(P)
+            if self.loss_channel_weights is not None:
+                ops.loss_edge_stats_w(P.pred, P.target, P.loss_edge_part, *dims, P.target.shape[1], self.loss_channel_weights,
+                                      self.loss_valid_min)
+                ops.loss_edge_final_w(P.loss_edge_part, P.loss_edge, P.losses, w, *dims, P.loss_counts)
+                return
             ops.loss_edge_stats(P.pred, P.target, P.loss_edge_part, *dims, **kw)
             ops.loss_edge_final(P.loss_edge_part, P.loss_edge, P.losses, w, *dims, **kw)
         return both
@@ -1099,9 +1118,18 @@ class TulipEngine:
         what the backward forms C from, on the device; L2: with the rest), then -- beside the chain when `defer` (run_backward
         issues it; nothing on the GPU reads `losses`) -- berHu's value pass and the final fold.
         With a mask (loss_valid_min; "l1" too) the masked launches, and the statistics at once for every kind: their counts are
-        what the backward forms n_v from."""
+        what the backward forms n_v from.  With channel weights (loss_channel_weights; every kind, masked or not) the weighted
+        launches in the masked ones' places: their counts are what the backward forms n_S from."""
         n, lt = P.pred.numel(), self.model.log_transform
-        if self.loss_valid_min is not None:
+        if self.loss_channel_weights is not None:
+            wargs = self._loss_w(P)
+            ops.loss_stats_w(P.pred, P.target, P.loss_stats, n, lt, *wargs, P.loss_counts)
+
+            def fin():
+                if kind == "berhu":
+                    ops.loss_value_w(P.pred, P.target, P.loss_stats, P.loss_vpart, n, *wargs, P.loss_counts)
+                ops.loss_final_w(kind, P.loss_stats, P.loss_vpart, P.losses, n, P.loss_counts, P.loss_valid)
+        elif self.loss_valid_min is not None:
             mask = self._loss_mask(P)
             ops.loss_stats_m(P.pred, P.target, P.loss_stats, n, lt, *mask, P.loss_counts)
 
@@ -1235,7 +1263,8 @@ class TulipEngine:
         loss_done = False
         kind = self.loss_kind
         # the L1 partial sums ride in the head's forward; another loss, and any loss over the valid pixels only, reads pred behind it
-        l1 = with_loss and kind == "l1" and self.loss_valid_min is None
+        # or with channel weights, reads pred behind it
+        l1 = with_loss and kind == "l1" and self.loss_valid_min is None and self.loss_channel_weights is None
         if m.pixel_shuffle and self.fuse_tail_fwd:
             # norm_up -> expand conv -> LeakyReLU -> PixelShuffle(4) -> decoder_pred (-> L1 partial sums) in ONE launch
             ops.tail_fwd_ln(x, W_.p32("norm_up.weight"), W_.p32("norm_up.bias"), self.eps, P["tail.xn"], P["tail.mean"],
@@ -1273,7 +1302,7 @@ class TulipEngine:
         self._join_pack()                          # (a model without fused wide blocks never asked for the copies)
         if with_loss and not loss_done and not l1:
             # (the masked read-out goes beside the chain with this head too)
-            self._loss_fwd(P, kind, defer_loss_final and self.loss_valid_min is not None)
+            self._loss_fwd(P, kind, defer_loss_final and (self.loss_valid_min is not None or self.loss_channel_weights is not None))
         elif with_loss and not loss_done:
             self._with_edge(P, lambda: ops.l1_loss_fwd(P.pred, P.target, P.partials, P.losses, P.pred.numel(), m.log_transform))()
         P.generation += 1
@@ -1986,10 +2015,15 @@ class TulipEngine:
         kind = self.loss_kind
         edge_w = self.loss_edge_weight
         # the head kernels form sign(pred - target) / n themselves -- unless the edge term has to be added to it: L1 then takes the
-        # dpred route of the other losses
-        l1 = kind == "l1" and self.loss_valid_min is None and edge_w == 0.0
-        l1_dpred = kind == "l1" and self.loss_valid_min is None and edge_w > 0.0
-        if l1_dpred:
+        # dpred route of the other losses, as it does with channel weights
+        cw = self.loss_channel_weights
+        l1 = kind == "l1" and self.loss_valid_min is None and edge_w == 0.0 and cw is None
+        l1_dpred = kind == "l1" and self.loss_valid_min is None and edge_w > 0.0 and cw is None
+        if cw is not None:
+            # ... over the counted elements (every kind): n_S from the forward's counts, g_c = w_c * g per channel, +0 at the others
+            ops.loss_bwd_w(kind, P.pred, P.target, P.loss_stats, gscale_dev, gscale, P.dpred, P.loss_c, P.pred.numel(),
+                           *self._loss_w(P), P.loss_counts, P.loss_valid)
+        elif l1_dpred:
             ops.l1_loss_bwd(P.pred, P.target, gscale_dev, gscale, P.dpred, P.pred.numel())
         elif self.loss_valid_min is not None:
             # ... over the valid pixels (every kind, "l1" too): n_v from the forward's counts in this launch, +0 at the others
@@ -2002,7 +2036,11 @@ class TulipEngine:
         if edge_w > 0.0:
             # ... + weight * gscale * d(edge)/d(pred), added in place (csrc/loss.hip, tulip_loss_edge_bwd)
             dims, ekw = self._edge_args(P)
-            ops.loss_edge_bwd(P.pred, P.target, gscale_dev, gscale, edge_w, P.dpred, *dims, **ekw)
+            if cw is not None:
+                ops.loss_edge_bwd_w(P.pred, P.target, gscale_dev, gscale, edge_w, P.dpred, *dims, P.target.shape[1], cw,
+                                    self.loss_valid_min, P.loss_counts)
+            else:
+                ops.loss_edge_bwd(P.pred, P.target, gscale_dev, gscale, edge_w, P.dpred, *dims, **ekw)
         if m.pixel_shuffle:
             tpart = P["tail.dwd_part"]
             head_w, head_b = "ps_head.conv_expand.0.weight", "ps_head.conv_expand.0.bias"
@@ -2234,7 +2272,7 @@ class TulipEngine:
         key = key + (self.fuse_wide, self.fuse_wide_bwd, self.fuse_block96, self.fuse_block96_bwd, self.split_wide, self.split_wide_bwd,
                      self.fc1_grad_wide, self.fc1_grad96, self.recompute96, self.fuse_deep, self.fuse_tail_fwd, self.fuse_tail_bwd, self.fuse_glue, self.pair96, self.packed_gemm,
                      int(self._drop_seed), int(self.n_drop_slots), self.dropout_state(), self.loss_kind, self.loss_valid_min,
-                     self.loss_edge_weight)
+                     self.loss_edge_weight, self.loss_channel_weights)
         ent = graphs.get(key)
         if not self.graph_module or ent is None:
             fn()

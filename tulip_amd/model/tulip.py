@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..loss import check_edge_weight, check_loss, check_valid_min
+from ..loss import check_channel_weights, check_edge_weight, check_loss, check_valid_min
 
 __all__ = ["TULIP", "tulip_base", "tulip_large"]
 
@@ -195,7 +195,17 @@ class TULIP(nn.Module):
     reference's util/filter.py modules, which tulip.py:9 imports and never calls) per (b, c) plane with zero padding; with
     loss_valid_min over the responses centred on a valid pixel, the difference taken as 0 at an invalid one (tulip_amd/loss.py is
     the definition).  pixel_loss does not change.  Fixed at construction; state_dict() does not carry it (ValueError for a bool,
-    an int, a NaN, an infinity or a negative value)."""
+    an int, a NaN, an infinity or a negative value).
+
+    loss_channel_weights: None (default: no weights -- no buffer, no launch, every result as without the keyword) or a tuple of
+    in_chans finite floats >= 0 with at least one > 0, (w_0, ..., w_{C-1}): range, intensity and the other channels have other
+    scales and other noise.  Element (b, c, y, x) is counted iff its pixel is valid (loss_valid_min; always without it) and
+    w_c > 0; with S the counted elements, total_loss = (1/n_S) sum_S w_c f(d) (the edge term: w_c times the plane's responses,
+    over n_S), the gradient w_c f'(d) / n_S on S and +0 off it, berHu's C the unweighted maximum over S, pixel_loss the unweighted
+    L1 metric over S (tulip_amd/loss.py is the definition).  A weight of 0 takes a channel out of the loss by selection -- an
+    auxiliary input channel that is not supervised; a NaN there changes nothing -- except that channel 0 of the target still
+    decides validity.  Per call, as n_v and C are.  Fixed at construction; state_dict() does not carry it (ValueError for a bool,
+    an int, a NaN, an infinity, a negative value, a wrong length or all zeros)."""
 
     def __init__(self, img_size=(32, 2048), target_img_size=(128, 2048), patch_size=(4, 4), in_chans: int = 1,
                  embed_dim: int = 96, window_size=4, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
@@ -203,11 +213,12 @@ class TULIP(nn.Module):
                  drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True,
                  pixel_shuffle: bool = False, circular_padding: bool = False, swin_v2: bool = False,
                  log_transform: bool = False, patch_unmerging: bool = False, loss: str = "l1",
-                 loss_valid_min=None, loss_edge_weight: float = 0.0):
+                 loss_valid_min=None, loss_edge_weight: float = 0.0, loss_channel_weights=None):
         super().__init__()
         self._loss = check_loss(loss)
         self._loss_valid_min = check_valid_min(loss_valid_min)
         self._loss_edge_weight = check_edge_weight(loss_edge_weight)
+        self._loss_channel_weights = check_channel_weights(loss_channel_weights, in_chans)
         self.window_size = window_size
         self.depths, self.num_heads = tuple(depths), tuple(num_heads)
         self.num_layers = len(depths)
@@ -284,6 +295,12 @@ class TULIP(nn.Module):
     def loss_edge_weight(self) -> float:
         """the weight of the edge term chosen at construction: 0.0 (no term) or a positive float (tulip_amd/loss.py)"""
         return self._loss_edge_weight
+
+    @property
+    def loss_channel_weights(self):
+        """the channel weights of the loss chosen at construction: None (no weights) or a tuple of in_chans floats
+        (tulip_amd/loss.py)"""
+        return self._loss_channel_weights
 
     # ------------------------------------------------------------------ engine plumbing
     def engine(self):

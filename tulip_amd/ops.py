@@ -875,3 +875,64 @@ def skip_unmerge_bwd(**kw):
     """tulip_skip_unmerge_bwd: the skip Linear's data gradient (unmerged half) -> PatchUnmerging's data gradient."""
     d = _fill(_lib.SkipUnmergeBwdDesc, kw, ("cast_rows_per_sample", "B", "H", "W", "C"), default=0)
     check(_lib.load().tulip_skip_unmerge_bwd(ctypes.byref(d), _stream()), "tulip_skip_unmerge_bwd")
+
+
+def _chan_weights(weights):
+    """the host array of a _w launch (None: NULL, which the library refuses)"""
+    import ctypes
+    return None if weights is None else (ctypes.c_float * len(weights))(*[float(w) for w in weights])
+
+
+def _w_mask(valid_min) -> tuple:
+    """(masked, valid_min) of a _w launch: valid_min None is the unmasked case"""
+    return (0, 0.0) if valid_min is None else (1, float(valid_min))
+
+
+def loss_stats_w(pred, target, stats, n, log_transform, chans, chan_stride, weights, valid_min, counts):
+    """loss_stats over the COUNTED elements (TULIP(loss_channel_weights=...), tulip_amd/loss.py: w_c > 0 and, valid_min not None,
+    a valid pixel): per workgroup [sum w_c |d|, the unweighted metric sum, sum w_c d^2, max |d|], and counts as in loss_stats_m.
+    weights: `chans` Python floats, passed by value in the launch arguments."""
+    check(_lib.load().tulip_loss_stats_w(_p(pred), _p(target), _p(stats), n, int(log_transform), int(chans), int(chan_stride),
+                                         _chan_weights(weights), *_w_mask(valid_min), _p(counts), _stream()), "tulip_loss_stats_w")
+
+
+def loss_bwd_w(kind, pred, target, stats, gscale_dev, gscale, dpred, loss_c, n, chans, chan_stride, weights, valid_min, counts,
+               n_valid):
+    """loss_bwd with g_c = w_c * gscale / n_S per channel, n_S = sum(counts), and +0 at the elements that are not counted; n_valid
+    (one int64) receives n_S."""
+    check(_lib.load().tulip_loss_bwd_w(_loss_kind(kind), _p(pred), _p(target), _p(stats), _p(gscale_dev), float(gscale), _p(dpred),
+                                       _p(loss_c), n, int(chans), int(chan_stride), _chan_weights(weights), *_w_mask(valid_min),
+                                       _p(counts), _p(n_valid), _stream()), "tulip_loss_bwd_w")
+
+
+def loss_value_w(pred, target, stats, value_partials, n, chans, chan_stride, weights, valid_min, counts):
+    """berhu's second pass over the counted elements, every value times its channel's weight."""
+    check(_lib.load().tulip_loss_value_w(_p(pred), _p(target), _p(stats), _p(value_partials), n, int(chans), int(chan_stride),
+                                         _chan_weights(weights), *_w_mask(valid_min), _p(counts), _stream()), "tulip_loss_value_w")
+
+
+def loss_final_w(kind, stats, value_partials, losses, n, counts, n_valid):
+    """losses[0] = the weighted loss of `kind`, losses[1] = the unweighted L1 metric over the counted elements (loss_stats_w's second
+    sums, whatever log_transform was), both over n_S = sum(counts); n_valid receives n_S."""
+    check(_lib.load().tulip_loss_final_w(_loss_kind(kind), _p(stats), _p(value_partials), _p(losses), n, _p(counts), _p(n_valid),
+                                         _stream()), "tulip_loss_final_w")
+
+
+def loss_edge_stats_w(pred, target, edge_partials, planes, H, W, chans, weights, valid_min):
+    """loss_edge_stats with every response times its plane's weight (plane p: channel p % chans); a plane of weight 0 is not read."""
+    check(_lib.load().tulip_loss_edge_stats_w(_p(pred), _p(target), _p(edge_partials), int(planes), int(H), int(W), int(chans),
+                                              _chan_weights(weights), *_w_mask(valid_min), _stream()), "tulip_loss_edge_stats_w")
+
+
+def loss_edge_bwd_w(pred, target, gscale_dev, gscale, weight, dpred, planes, H, W, chans, weights, valid_min, counts):
+    """loss_edge_bwd with ge_c = weight * w_c * gscale / n_S per plane, n_S from `counts` (loss_stats_w's); a plane of weight 0 is
+    neither read nor written."""
+    check(_lib.load().tulip_loss_edge_bwd_w(_p(pred), _p(target), _p(gscale_dev), float(gscale), float(weight), _p(dpred), int(planes),
+                                            int(H), int(W), int(chans), _chan_weights(weights), *_w_mask(valid_min), _p(counts),
+                                            _stream()), "tulip_loss_edge_bwd_w")
+
+
+def loss_edge_final_w(edge_partials, edge_out, losses, weight, planes, H, W, counts):
+    """loss_edge_final with 1 / n_S from `counts`."""
+    check(_lib.load().tulip_loss_edge_final_w(_p(edge_partials), _p(edge_out), _p(losses), float(weight), int(planes), int(H), int(W),
+                                              _p(counts), _stream()), "tulip_loss_edge_final_w")

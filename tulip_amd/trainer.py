@@ -36,7 +36,7 @@ from .clip import check_clip_grad
 from .ddp import GradBucketer
 from .ema import ParamEMA, check_decay
 from .guard import check_skip_nonfinite
-from .loss import check_edge_weight, check_loss, check_valid_min
+from .loss import check_channel_weights, check_edge_weight, check_loss, check_valid_min
 from .engine import ALIGN
 
 
@@ -126,7 +126,12 @@ class Trainer:
         The edge term is the model's as well (TULIP(loss_edge_weight=w)): with w > 0 `losses[0]` is the total, the loss above plus
         w times the mean Sobel response of pred - target, formed on the device inside the captured graphs per micro-batch and
         per rank; `edge_loss` is the device float of the last forward's term (AttributeError at w == 0).  exchange="sharded" with
-        w > 0 raises ValueError; state_dict() records w as "loss_edge_weight"."""
+        w > 0 raises ValueError; state_dict() records w as "loss_edge_weight".
+        The channel weights are the model's (TULIP(loss_channel_weights=(w_0, ..))): the loss, its gradient and the edge term then
+        weigh channel c by w_c over the counted elements (valid pixels of the channels with w_c > 0), n_S of them counted on the
+        device per micro-batch and per rank (`loss_valid` is that count); `losses[1]` stays the unweighted L1 metric over them.  A
+        NaN in a w_c == 0 channel costs no step under skip_nonfinite.  exchange="sharded" with weights raises ValueError;
+        state_dict() records them as "loss_channel_weights", only when they are set."""
         skip_nonfinite = check_skip_nonfinite(skip_nonfinite)
         self.loss = check_loss(getattr(model, "loss", "l1"))
         self.loss_valid_min = check_valid_min(getattr(model, "loss_valid_min", None))
@@ -137,6 +142,10 @@ class Trainer:
         self.loss_edge_weight = check_edge_weight(getattr(model, "loss_edge_weight", 0.0))
         if self.loss_edge_weight != 0.0 and exchange == "sharded":
             raise ValueError("exchange='sharded' with loss_edge_weight is not supported: use exchange='allreduce'")
+        cw = getattr(model, "loss_channel_weights", None)
+        self._loss_channel_weights = None if cw is None else check_channel_weights(tuple(cw), model.in_chans)
+        if self._loss_channel_weights is not None and exchange == "sharded":
+            raise ValueError("exchange='sharded' with loss_channel_weights is not supported: use exchange='allreduce'")
         if skip_nonfinite and exchange == "sharded":
             raise ValueError("exchange='sharded' with skip_nonfinite is not supported (the per-bucket optimizer steps before the "
                              "global norm exists): use exchange='allreduce'")
@@ -366,10 +375,15 @@ class Trainer:
     @property
     def loss_valid(self) -> torch.Tensor:
         """n_v, the valid elements (in_chans per valid pixel) of the last backward's loss: a device int64 (no sync); models built
-        with loss_valid_min only."""
-        if self.loss_valid_min is None:
+        with loss_valid_min only -- or with loss_channel_weights: n_S, the counted elements."""
+        if self.loss_valid_min is None and self._loss_channel_weights is None:
             raise AttributeError("this Trainer's model has no valid-pixel mask: build the model with loss_valid_min=...")
         return self.P.loss_valid
+
+    @property
+    def loss_channel_weights(self):
+        """The model's channel weights (TULIP(loss_channel_weights=...)): None or a tuple of in_chans floats."""
+        return self._loss_channel_weights
 
     @property
     def edge_loss(self) -> torch.Tensor:
@@ -591,6 +605,8 @@ class Trainer:
             sd["clip_grad"] = self._clip_grad
         if self.skip_nonfinite:                    # (likewise)
             sd["guard"] = {"applied": applied, "skipped": skipped, "consecutive": consecutive}
+        if self._loss_channel_weights is not None:
+            sd["loss_channel_weights"] = tuple(self._loss_channel_weights)
         return sd
 
     def _report_saved_edge_weight(self, sd: dict) -> bool:
@@ -602,6 +618,17 @@ class Trainer:
             return False
         sys.stderr.write(f"tulip_amd.Trainer: the optimizer state was saved with loss_edge_weight={saved!r} and this Trainer's model "
                          f"was built with {self.loss_edge_weight!r}: the model's value stays\n")
+        return True
+
+    def _report_saved_channel_weights(self, sd: dict) -> bool:
+        """The channel weights are the model's setting too, and follow the edge weight's rule: a state saved under other weights (a
+        dictionary without the key: None) is loaded all the same and the difference is reported on stderr.  True when they differ."""
+        saved = sd.get("loss_channel_weights")
+        saved = None if saved is None else tuple(float(w) for w in saved)
+        if saved == self._loss_channel_weights:
+            return False
+        sys.stderr.write(f"tulip_amd.Trainer: the optimizer state was saved with loss_channel_weights={saved!r} and this Trainer's "
+                         f"model was built with {self._loss_channel_weights!r}: the model's value stays\n")
         return True
 
     def load_state_dict(self, sd: dict) -> None:
@@ -627,6 +654,7 @@ class Trainer:
             sys.stderr.write("tulip_amd.Trainer: the optimizer state was saved with gradient clipping ('clip_grad') and this Trainer "
                              "clips nothing (clip_grad=None): ignored\n")
         self._report_saved_edge_weight(sd)
+        self._report_saved_channel_weights(sd)
         put = lambda flat, n, t: flat[W.offset[n]:W.offset[n] + W.numel[n]].copy_(t.reshape(-1).to(flat.dtype))
         for n in W.names:
             put(self.m, n, sd["exp_avg"][n])

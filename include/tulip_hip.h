@@ -874,6 +874,34 @@ int tulip_range_to_xyz_durlar(const float* img, const double* col_tables, const 
                               const int32_t* row_offset, float max_range, float origin_offset, double z_offset, int H,
                               int W, double* xyz, hipStream_t stream);
 
+/* ---- dense point clouds from a batch of predictions (csrc/cloud.hip; tulip_amd/cloud.py is the host definition) ----
+ *
+ * pred (B,C,H,W), lo (B,C,h,w), C = 1..4.  Per image: the prediction side of tulip_eval_postprocess (C = 1) /
+ * tulip_eval_postprocess_c (C >= 2) without a target -- expm1, inclusive gate, rows 0::H/h restored from lo iff w == W,
+ * keep_close -- then the projection of tulip_range_to_xyz / tulip_range_to_xyz_durlar (the float64 DurLAR point rounded once to
+ * float32), and an ordered compaction that keeps the pixels whose final range is > 0.0f (false for -0.0f, +0.0f and a NaN).
+ * Row order: the row order of the projection's output (row-major; DurLAR: the staggered index v*W + (u + W - row_offset[v]) % W)
+ * with the other rows removed; images concatenated.  A row is (x, y, z, a_1 .. a_{C-1}), a_c = the final value of channel c.
+ *
+ * Outputs: rng (B,C,H,W) the post-processed planes in that row ("destination") order -- for the spherical sensors the planes
+ * tulip_eval_postprocess(_c) writes to pred_img; counts (B*tiles int32, tiles = ceil(H*W / tulip_cloud_tile())) the kept slots of
+ * every tile; tile_offsets (B*tiles int64) their exclusive scan; offsets (B+1 int64): image b owns rows offsets[b] ..
+ * offsets[b+1]-1, offsets[0] = 0; points (capacity B*H*W rows of 3+C-1 floats): rows at or beyond offsets[B] are not written.
+ * Three stream-ordered launches (post-process + count, scan by one block, write); no block waits for another.
+ *
+ * TULIP_ERR_ARG before any launch: a null pointer, C outside 1..4, B, H, W, h or w <= 0, B > 65535, H % h, chan_log_bits at or
+ * above bit C-1. */
+int tulip_cloud_tile(void);
+int tulip_cloud_spherical(const float* pred, const float* lo, int B, int C, int H, int W, int h, int w, int log_transform,
+                          uint32_t chan_log_bits, float gate_min, float gate_max, float keep_close, float max_range,
+                          const float* sin_h, const float* cos_h, const float* sin_v, const float* cos_v, float* rng,
+                          int32_t* counts, int64_t* tile_offsets, int64_t* offsets, float* points, hipStream_t stream);
+int tulip_cloud_durlar(const float* pred, const float* lo, int B, int C, int H, int W, int h, int w, int log_transform,
+                       uint32_t chan_log_bits, float gate_min, float gate_max, float keep_close, float max_range,
+                       const double* col_tables, const double* row_tables, const int32_t* row_offset, float origin_offset,
+                       double z_offset, float* rng, int32_t* counts, int64_t* tile_offsets, int64_t* offsets, float* points,
+                       hipStream_t stream);
+
 /* Voxel IoU / precision / recall / F1 of two clouds (engine_upsampling.py:254-271; evaluation.py
  * voxelize_point_cloud :148-160, calculate_metrics :162-175).  Points (n,3) float32 (is_f64=0) or float64; voxel
  * of p = ((p - min)/grid_size).astype(int) with min/max over BOTH clouds, evaluated in the clouds' own type.

@@ -242,6 +242,10 @@ SIGNATURES = {
     "tulip_eval_postprocess_c": [P, P, P, P, P, P, P, I, I, I, I, I, I, ctypes.c_uint32, F, F, F, P],
     "tulip_range_to_xyz": [P, P, P, P, P, F, I, I, P, P],
     "tulip_range_to_xyz_durlar": [P, P, P, P, F, F, D, I, I, P, P],
+    # dense point clouds from a batch of predictions (csrc/cloud.hip; tulip_amd/cloud.py is the host definition)
+    "tulip_cloud_tile": [],
+    "tulip_cloud_spherical": [P, P, I, I, I, I, I, I, I, ctypes.c_uint32, F, F, F, F, P, P, P, P, P, P, P, P, P, P],
+    "tulip_cloud_durlar": [P, P, I, I, I, I, I, I, I, ctypes.c_uint32, F, F, F, F, P, P, P, F, D, P, P, P, P, P, P],
     "tulip_voxel_metrics": [P, L, P, L, I, D, P, P, L, P, P, P],
     "tulip_chamfer_sq": [P, L, P, L, I, P, P, P, P, P],
     "tulip_merge_fwd_supported": [I, I, I, I],

@@ -20,7 +20,7 @@ import json
 import math
 import numbers
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -62,6 +62,45 @@ def pred_gate(dataset_select: str, mc_drop: bool):
     raise NotImplementedError(f"Cannot find the dataset: {dataset_select}")       # engine:252-253
 
 
+class SensorGeometry(NamedTuple):
+    """Host tables of a dataset's range image -> point cloud projection (RangeEvaluator and cloud.CloudUpsampler upload them)."""
+    f64: bool                 # DurLAR: float64 points and the staggered pixel index
+    tables: tuple             # spherical sensors: (sin_h, cos_h) over columns, (sin_v, cos_v) over rows, float32
+    colt: Optional[np.ndarray]    # DurLAR: [cos(enc+az) | sin(enc+az) | o*cos(enc) | o*sin(enc)] (4*W) float64
+    rowt: Optional[np.ndarray]    # DurLAR: [cos(el) | sin(el)] (2*H) float64
+    z_lo: float               # sines of the lowest / highest beam
+    z_hi: float
+
+
+def sensor_geometry(dataset_select: str, H: int, W: int) -> SensorGeometry:
+    """The projection tables of util/evaluation.py img_to_pcd_kitti / _carla / _durlar for an (H, W) range image."""
+    if dataset_select == "kitti":
+        if (H, W) != (64, 1024):          # img_to_pcd_kitti hard-codes the sensor grid (evaluation.py:53-57)
+            raise ValueError(f"cannot reshape array of size {H * W} into shape ({64 * 1024},)")
+        ang_res_y, ang_res_x = 26.8 / (H - 1), 360 / W
+        v = np.float32(np.arange(H, dtype=np.float64) * ang_res_y) - 24.8           # :69
+        hz = -np.float32(np.arange(W, dtype=np.float64) + 1 - (W / 2)) * ang_res_x + 90.0   # :70
+        v, hz = v / 180.0 * np.pi, hz / 180.0 * np.pi                              # :72-73
+        z_lo, z_hi = math.sin(math.radians(-24.8)), math.sin(math.radians(2.0))
+    elif dataset_select == "carla":
+        v = np.deg2rad(np.linspace(start=-15, stop=15, num=H).astype(np.float32))           # :94,:105-106
+        hz = np.deg2rad(np.linspace(start=-180, stop=180, num=W, endpoint=False).astype(np.float32))
+        z_lo, z_hi = math.sin(math.radians(-15)), math.sin(math.radians(15))
+    else:
+        if H > len(DURLAR_ELEVATION_DEG):
+            raise IndexError(f"index {H - 1} is out of bounds for axis 0 with size {len(DURLAR_ELEVATION_DEG)}")
+        u = np.arange(W)
+        enc = 2.0 * math.pi - (((W + u) % W) * (math.pi * 2.0 / W))                 # :28-30
+        el = math.pi * np.array(DURLAR_ELEVATION_DEG[:H], dtype=np.float64) / 180.  # :32
+        colt = np.concatenate([np.cos(enc + DURLAR_ANGLE_OFF), np.sin(enc + DURLAR_ANGLE_OFF),
+                               DURLAR_ORIGIN_OFFSET * np.cos(enc), DURLAR_ORIGIN_OFFSET * np.sin(enc)])
+        rowt = np.concatenate([np.cos(el), np.sin(el)])
+        return SensorGeometry(True, (), colt, rowt, math.sin(el.min()), math.sin(el.max()))
+    assert v.dtype == np.float32 and hz.dtype == np.float32
+    tables = tuple(np.ascontiguousarray(t) for t in (np.sin(hz), np.cos(hz), np.sin(v), np.cos(v)))
+    return SensorGeometry(False, tables, None, None, z_lo, z_hi)
+
+
 class RangeEvaluator:
     """Per-image metrics of one dataset configuration.  `__call__(pred, lo, hi)` takes (1,1,H,W)/(1,1,h,w) device
     tensors in the model's value space and returns a device float64 tensor ordered as RESULT_COLUMNS; nothing
@@ -82,38 +121,15 @@ class RangeEvaluator:
             raise RuntimeError("tulip_amd.evaluation runs on the GPU only (HIP kernels, no CPU fallback)")
         H, W, dev = self.H, self.W, self.device
         R = MAX_RANGE[dataset_select]
-        if dataset_select == "kitti":
-            if (H, W) != (64, 1024):          # img_to_pcd_kitti hard-codes the sensor grid (evaluation.py:53-57)
-                raise ValueError(f"cannot reshape array of size {H * W} into shape ({64 * 1024},)")
-            self.f64 = False
-            ang_res_y, ang_res_x = 26.8 / (H - 1), 360 / W
-            v = np.float32(np.arange(H, dtype=np.float64) * ang_res_y) - 24.8           # :69
-            hz = -np.float32(np.arange(W, dtype=np.float64) + 1 - (W / 2)) * ang_res_x + 90.0   # :70
-            v, hz = v / 180.0 * np.pi, hz / 180.0 * np.pi                              # :72-73
-            z_lo, z_hi = math.sin(math.radians(-24.8)), math.sin(math.radians(2.0))
-        elif dataset_select == "carla":
-            self.f64 = False
-            v = np.deg2rad(np.linspace(start=-15, stop=15, num=H).astype(np.float32))           # :94,:105-106
-            hz = np.deg2rad(np.linspace(start=-180, stop=180, num=W, endpoint=False).astype(np.float32))
-            z_lo, z_hi = math.sin(math.radians(-15)), math.sin(math.radians(15))
-        else:
-            if H > len(DURLAR_ELEVATION_DEG):
-                raise IndexError(f"index {H - 1} is out of bounds for axis 0 with size {len(DURLAR_ELEVATION_DEG)}")
-            self.f64 = True
-            u = np.arange(W)
-            enc = 2.0 * math.pi - (((W + u) % W) * (math.pi * 2.0 / W))                 # :28-30
-            el = math.pi * np.array(DURLAR_ELEVATION_DEG[:H], dtype=np.float64) / 180.  # :32
-            colt = np.concatenate([np.cos(enc + DURLAR_ANGLE_OFF), np.sin(enc + DURLAR_ANGLE_OFF),
-                                   DURLAR_ORIGIN_OFFSET * np.cos(enc), DURLAR_ORIGIN_OFFSET * np.sin(enc)])
-            rowt = np.concatenate([np.cos(el), np.sin(el)])
-            self.colt = torch.from_numpy(colt).to(dev)
-            self.rowt = torch.from_numpy(rowt).to(dev)
+        geo = sensor_geometry(dataset_select, H, W)
+        self.f64 = geo.f64
+        if self.f64:
+            self.colt = torch.from_numpy(geo.colt).to(dev)
+            self.rowt = torch.from_numpy(geo.rowt).to(dev)
             self.row_offset = torch.tensor(DURLAR_PIXEL_OFFSET[:H], dtype=torch.int32, device=dev)
-            z_lo, z_hi = math.sin(el.min()), math.sin(el.max())
-        if not self.f64:
-            assert v.dtype == np.float32 and hz.dtype == np.float32
-            self.tables = [torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-                           for t in (np.sin(hz), np.cos(hz), np.sin(v), np.cos(v))]
+        else:
+            self.tables = [torch.from_numpy(t).to(dev) for t in geo.tables]
+        z_lo, z_hi = geo.z_lo, geo.z_hi
         # voxel bitmaps: an upper bound of the grid from the sensor geometry (the reference sizes it from the data)
         Rb = R * _VALUE_BOUND[dataset_select] + 0.1
         dims = [int(2 * Rb / self.grid_size) + 2] * 2 + [int(Rb * (max(z_hi, 0) - min(z_lo, 0)) / self.grid_size) + 3]

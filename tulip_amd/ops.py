@@ -607,6 +607,38 @@ def range_to_xyz_durlar(img, col_tables, row_tables, row_offset, max_range, orig
                                                 _p(xyz), _stream()), "tulip_range_to_xyz_durlar")
 
 
+# ---- dense point clouds (csrc/cloud.hip; tulip_amd/cloud.py is the host definition)
+def cloud_tile() -> int:
+    """tulip_cloud_tile: destination slots per block; counts / tile_offsets hold B * ceil(H*W / cloud_tile()) entries"""
+    return _lib.load().tulip_cloud_tile()
+
+
+def _cloud_common(pred, lo, B, C, H, W, h, w, log_transform, chan_log, gate_min, gate_max, keep_close, max_range):
+    mask = sum(1 << k for k, on in enumerate(chan_log or ()) if on)
+    return (_p(pred), _p(lo), int(B), int(C), int(H), int(W), int(h), int(w), int(log_transform), mask, float(gate_min),
+            float(gate_max), float(keep_close), float(max_range))
+
+
+def cloud_spherical(pred, lo, B, C, H, W, h, w, log_transform, chan_log, gate_min, gate_max, keep_close, max_range, sin_h, cos_h,
+                    sin_v, cos_v, rng, counts, tile_offsets, offsets, points):
+    """tulip_cloud_spherical: pred (B,C,H,W), lo (B,C,h,w) -> rng (B,C,H,W), counts int32 / tile_offsets int64 (B*tiles),
+    offsets int64 (B+1), points float32 (B*H*W, 3+C-1).  chan_log: the C-1 log flags of channels 1..C-1."""
+    check(_lib.load().tulip_cloud_spherical(*_cloud_common(pred, lo, B, C, H, W, h, w, log_transform, chan_log, gate_min,
+                                                            gate_max, keep_close, max_range),
+                                            _p(sin_h), _p(cos_h), _p(sin_v), _p(cos_v), _p(rng), _p(counts), _p(tile_offsets),
+                                            _p(offsets), _p(points), _stream()), "tulip_cloud_spherical")
+
+
+def cloud_durlar(pred, lo, B, C, H, W, h, w, log_transform, chan_log, gate_min, gate_max, keep_close, max_range, col_tables,
+                 row_tables, row_offset, origin_offset, z_offset, rng, counts, tile_offsets, offsets, points):
+    """tulip_cloud_durlar: cloud_spherical with the DurLAR tables; rows and rng are in the staggered destination order."""
+    check(_lib.load().tulip_cloud_durlar(*_cloud_common(pred, lo, B, C, H, W, h, w, log_transform, chan_log, gate_min, gate_max,
+                                                         keep_close, max_range),
+                                         _p(col_tables), _p(row_tables), _p(row_offset), float(origin_offset), float(z_offset),
+                                         _p(rng), _p(counts), _p(tile_offsets), _p(offsets), _p(points), _stream()),
+          "tulip_cloud_durlar")
+
+
 def voxel_metrics(pcd_pred, n_pred, pcd_gt, n_gt, is_f64, grid_size, bitmap_pred, bitmap_gt, bitmap_words, scratch,
                   out):
     check(_lib.load().tulip_voxel_metrics(_p(pcd_pred), n_pred, _p(pcd_gt), n_gt, int(is_f64), float(grid_size),
